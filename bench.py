@@ -21,7 +21,17 @@ drop-in for process_incoming_job) on 256 config-5 symbols as DBXCOL1 payloads in
 payload validation and staging, H2D, the kernel, the summaries' read-back and the
 CompleteRequest.data strings — and prints its own JSON line.
 
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print
+the line. `--full` adds the legs that take runs of their own: today the CPU baseline (the C
+oracle on the same shard, ~35 s), reported as `cpu_baseline` in the line.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64): the
+top-k records and run counters the step returns, and the engine's per-(symbol, parameter)
+summaries of a fixed, seeded sample of rank 0's symbols. The inputs depend on the arguments
+alone, so two builds run with the same arguments can be compared array for array.
+
 Run: python bench.py [--gpus N --steps K --warmup W] [--config C] [--scaling weak|strong]
+                     [--full] [--dump-outputs DIR]
      torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 """
 from __future__ import annotations
@@ -145,6 +155,38 @@ def cpu_baseline(cfg, grid, sym0, shard, target_thread_s=25.0, target_1t_s=8.0):
             "model": cpus["model"]}
 
 
+DUMP_SEED = 0xD0C5
+DUMP_SUMMARY_BYTES = 40 << 20  # the summaries' share of the 64 MB a dump may take
+DUMP_SUMMARY_ROWS = 1024
+
+
+def dump_outputs(path, eng, top, counters, sym0, n_sym, P):
+    """What the last timed step computed, as float64 .npy files under `path`: the top-k records
+    and [bar-evals, trades] the step returned (over every rank at N > 1), and the engine's
+    summaries (this rank's shard, one row per sampled symbol, one column per parameter) of a
+    seeded sample of symbols, the same sample whenever the shard is the same. The 64-bit trade
+    hash goes out as two exact 32-bit halves."""
+    os.makedirs(path, exist_ok=True)
+
+    def put(name, a):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    if top is not None:
+        top = np.asarray(top, D.TOPK_DTYPE)
+        for f in D.TOPK_DTYPE.names:
+            put("topk_" + f, top[f])
+        put("counters", np.asarray(counters, dtype=np.float64))
+    fields = [f for f in D.SUMMARY_DTYPE.names if f != "hash"]
+    rows = max(1, min(n_sym, DUMP_SUMMARY_ROWS, DUMP_SUMMARY_BYTES // (8 * P * (len(fields) + 2))))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_sym, size=rows, replace=False))
+    got = eng.summaries()[pick]
+    put("summary_symbols", sym0 + pick)
+    for f in fields:
+        put("summary_" + f, got[f])
+    put("summary_hash_lo", got["hash"] & np.uint64(0xFFFFFFFF))
+    put("summary_hash_hi", got["hash"] >> np.uint64(32))
+
+
 def load_pmc(config):
     """Measured HBM bytes and VALU instructions per launch of the dominant kernel from the
     committed rocprofv3 PMC summaries (profiles/pmc_config<C>.json, written by
@@ -169,7 +211,13 @@ def main():
     ap.add_argument("--leg", choices=["kernel", "ingest"], default="kernel")
     ap.add_argument("--topk", type=int, default=TOPK,
                     help="0 skips the top-k chain (profiling-build ablations, where Sharpes tie)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own (N = 1: the CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes the last step's outputs to "
+                         "DIR/<name>.npy (float64)")
     ap.add_argument("--segments", type=int, default=0,
                     help="bar segments per symbol (bt_set_segments): 0 = automatic, 1 = off")
     ap.add_argument("--burn", type=int, default=0,
@@ -178,6 +226,8 @@ def main():
                     help="after timing, rank 0 runs every rank's symbols in one engine and asserts "
                          "that the exchanged top-k and counters equal it (N > 1 rehearsals)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.leg == "ingest":
         return ingest_leg(args)
     cfg = CONFIGS[args.config]
@@ -350,6 +400,8 @@ def main():
     # bar segments per symbol of the last run and the blocks its fix passes re-walked (read
     # after the timed region: the count is a device read-back)
     n_seg, refixed = eng.last_segments(with_refixed=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, top, counters, sym0, n_sym, P)
 
     verified = None
     if args.verify and rank == 0 and topk > 0:
@@ -410,7 +462,7 @@ def main():
             line["per_rank"] = per_rank
         if verified is not None:
             line["verified_exchange"] = verified
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, grid, sym0, n_sym)
         print(json.dumps(line), flush=True)
     if comm is not None:

@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 NAME=$1; shift
 O=gpurun_out/prof/$NAME; mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o trace -- python3 bench.py "$@" > $O/bench.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o trace -- python3 bench.py "$@" --full > $O/bench.log 2>&1
 rc=$?; if [ $rc -ne 0 ]; then echo "trace $NAME failed rc=$rc"; tail -5 $O/bench.log; exit $rc; fi
 grep '^{' $O/bench.log | tail -1 | cut -c1-400
 PM="--steps 3 --warmup 1 --no-cpu-baseline"

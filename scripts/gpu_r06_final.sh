@@ -9,5 +9,5 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeou
 rc=$?; tail -3 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python3 -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > $O/smoke.log 2>&1
 rc=$?; tail -2 $O/smoke.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python3 bench.py > $O/bench_default.log 2>&1
+timeout -k 10 400 python3 bench.py --full > $O/bench_default.log 2>&1
 rc=$?; tail -1 $O/bench_default.log | cut -c1-600; exit $rc
