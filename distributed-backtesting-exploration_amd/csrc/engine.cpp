@@ -18,6 +18,7 @@
 #include <exception>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "csv.h"
@@ -138,6 +139,9 @@ struct bt_engine {
     hipEvent_t ev_batch[4] = {nullptr, nullptr, nullptr, nullptr};
     bt_batch_profile prof{};
     int64_t n_errors = 0;
+    // bt_replay: device staging of one chunk of requests (descriptors, summaries, trades, curves),
+    // at most kReplayBudget bytes whatever n and stride are
+    DevBuf<uint8_t> d_replay;
 };
 
 namespace {
@@ -461,6 +465,101 @@ void run_impl(bt_engine* e) {
         e->tdone_armed[b] = true;
     }
     e->ran = true;
+}
+
+// ---- bt_replay: chosen lanes again, with their trades and curves (k_replay.hip)
+// Device staging per call is bounded by this budget: the requests are processed in chunks of as
+// many lanes as fit (one lane of the longest symbol, 2^22 bars, with its curves and a full trade
+// list needs 37.7 + 134 MB, so one lane always fits).
+constexpr size_t kReplayBudget = 256u << 20;
+
+int32_t replay_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
+                    int32_t* n_bars, bt_trade* trades, int64_t* equity, int8_t* pos, int64_t stride) {
+    auto refuse = [](const std::string& m) { throw HipFail{"bt_replay: " + m}; };
+    if (!e) refuse("null engine");
+    if (e->syms.empty()) refuse("no dataset loaded");
+    if (n < 0 || n > BT_REPLAY_MAX)
+        refuse("n = " + std::to_string(n) + " outside [0, " + std::to_string(BT_REPLAY_MAX) + "]");
+    if (trade_cap < 0) refuse("trade_cap = " + std::to_string(trade_cap) + " is negative");
+    if (trades && trade_cap == 0) refuse("trades given with trade_cap = 0");
+    if (!trades && trade_cap > 0)
+        refuse("trade_cap = " + std::to_string(trade_cap) + " without a trades buffer");
+    if (n == 0) return 0;
+    if (!lanes || !sum) refuse("lanes and sum are required");
+    // global symbol id -> row; the first row of a repeated id wins
+    std::unordered_map<int32_t, int32_t> row;
+    row.reserve(e->syms.size());
+    for (size_t s = 0; s < e->syms.size(); ++s) row.emplace(e->syms[s].id, (int32_t)s);
+    std::vector<ReplayLane> req((size_t)n);
+    int32_t W = 0;  // the longest requested symbol
+    for (int32_t i = 0; i < n; ++i) {
+        const auto it = row.find(lanes[i].sym);
+        if (it == row.end())
+            refuse("unknown symbol id " + std::to_string(lanes[i].sym) + " (lane " + std::to_string(i) + ")");
+        if (lanes[i].param < 0 || lanes[i].param >= e->P)
+            refuse("param " + std::to_string(lanes[i].param) + " outside [0, " + std::to_string(e->P) +
+                   ") (lane " + std::to_string(i) + ")");
+        const SymDesc& sd = e->syms[(size_t)it->second];
+        req[i] = ReplayLane{sd.off, sd.bars, lanes[i].param};
+        W = std::max(W, sd.bars);
+    }
+    const bool curves = equity || pos;
+    if (curves && stride < W)
+        refuse("stride = " + std::to_string(stride) + " shorter than the longest requested symbol (" +
+               std::to_string(W) + " bars)");
+    activate(e);
+    sync_all(e);
+    // a lane closes at most one trade per bar: the device rows never need more than W slots
+    const int64_t dcap = std::min<int64_t>(trade_cap, W);
+    const int64_t pitch = curves ? std::min<int64_t>(stride, align_rows(W)) : 0;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t per_lane = sizeof(ReplayLane) + sizeof(bt_summary) + (size_t)dcap * sizeof(bt_trade) +
+                            (equity ? (size_t)pitch * 8 : 0) + (pos ? (size_t)pitch : 0);
+    const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, (kReplayBudget - 5 * 256) / per_lane));
+    const size_t o_lane = 0, o_sum = up(chunk * sizeof(ReplayLane));
+    const size_t o_tr = o_sum + up(chunk * sizeof(bt_summary));
+    const size_t o_eq = o_tr + up(chunk * (size_t)dcap * sizeof(bt_trade));
+    const size_t o_pos = o_eq + (equity ? up(chunk * (size_t)pitch * 8) : 0);
+    const size_t total = o_pos + (pos ? up(chunk * (size_t)pitch) : 0);
+    e->d_replay.ensure(total);
+    uint8_t* base = e->d_replay.p;
+    ReplayOut out{};
+    out.sum = reinterpret_cast<bt_summary*>(base + o_sum);
+    out.trades = dcap ? reinterpret_cast<bt_trade*>(base + o_tr) : nullptr;
+    out.trade_cap = (int32_t)dcap;
+    out.equity = equity ? reinterpret_cast<int64_t*>(base + o_eq) : nullptr;
+    out.pos = pos ? reinterpret_cast<int8_t*>(base + o_pos) : nullptr;
+    out.pitch = pitch;
+    // rows of a host array -> rows of a device one: one copy when the pitches agree, else a 2-D
+    // copy and the host tails zeroed here
+    auto fetch = [&](void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t m) {
+        if (dst_pitch == src_pitch) {
+            HIPCHK(hipMemcpyAsync(dst, src, m * src_pitch, hipMemcpyDeviceToHost, e->stream));
+            return;
+        }
+        HIPCHK(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, src_pitch, m, hipMemcpyDeviceToHost, e->stream));
+        for (size_t i = 0; i < m; ++i)
+            memset(static_cast<uint8_t*>(dst) + i * dst_pitch + src_pitch, 0, dst_pitch - src_pitch);
+    };
+    for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
+        const size_t m = std::min(chunk, (size_t)n - i0);
+        HIPCHK(hipMemcpyAsync(base + o_lane, req.data() + i0, m * sizeof(ReplayLane), hipMemcpyHostToDevice, e->stream));
+        if (dcap) HIPCHK(hipMemsetAsync(base + o_tr, 0, m * (size_t)dcap * sizeof(bt_trade), e->stream));
+        if (equity) HIPCHK(hipMemsetAsync(base + o_eq, 0, m * (size_t)pitch * 8, e->stream));
+        if (pos) HIPCHK(hipMemsetAsync(base + o_pos, 0, m * (size_t)pitch, e->stream));
+        HIPCHK(launch_replay(reinterpret_cast<const ReplayLane*>(base + o_lane), (int32_t)m, e->d_h.p, e->d_l.p,
+                             e->d_c.p, e->grid, out, e->stream));
+        HIPCHK(hipMemcpyAsync(sum + i0, out.sum, m * sizeof(bt_summary), hipMemcpyDeviceToHost, e->stream));
+        if (dcap)
+            fetch(trades + i0 * (size_t)trade_cap, (size_t)trade_cap * sizeof(bt_trade), out.trades,
+                  (size_t)dcap * sizeof(bt_trade), m);
+        if (equity) fetch(equity + i0 * (size_t)stride, (size_t)stride * 8, out.equity, (size_t)pitch * 8, m);
+        if (pos) fetch(pos + i0 * (size_t)stride, (size_t)stride, out.pos, (size_t)pitch, m);
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    if (n_bars)
+        for (int32_t i = 0; i < n; ++i) n_bars[i] = req[i].bars;
+    return n;
 }
 
 void drain_timing(bt_engine* e) {
@@ -864,6 +963,7 @@ void bt_engine_destroy(bt_engine* e) {
         e->d_segema.release();
         e->d_refixed.release();
         e->d_dbg.release();
+        e->d_replay.release();
         e->d_hist.release();
         e->d_counts.release();
         e->d_state.release();
@@ -1105,6 +1205,11 @@ int32_t bt_read_close(bt_engine* e, int32_t sym_index, int32_t* out, int32_t n) 
         HIPCHK(hipMemcpy(out, e->d_c.p + sd.off, (size_t)n * 4, hipMemcpyDeviceToHost));
         return 0;
     })
+}
+
+int32_t bt_replay(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
+                  int32_t* n_bars, bt_trade* trades, int64_t* equity, int8_t* pos, int64_t stride) {
+    ABI_GUARD(-1, { return replay_impl(e, n, lanes, trade_cap, sum, n_bars, trades, equity, pos, stride); })
 }
 
 int32_t bt_read_debug(bt_engine* e, uint64_t* out, int32_t n) {

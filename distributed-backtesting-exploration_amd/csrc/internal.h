@@ -157,6 +157,26 @@ hipError_t launch_boll(const SymDesc* syms, int32_t n_sym, const int32_t* high, 
 // Segments per symbol the Bollinger launcher would choose for this shard (auto mode).
 int32_t boll_auto_segments(int32_t n_sym, int32_t n_params, int32_t max_bars);
 
+// Replay of chosen lanes (k_replay.hip, bt_replay): one wave64 workgroup per request, which walks
+// the symbol's rows and writes its summary, its first trade_cap trades and, when asked, E_t and
+// pos_t of every bar. The buffers hold one chunk of requests; the host zeroes them before the
+// launch (the kernel writes only trades that happen and bars that exist).
+struct ReplayLane {
+    int64_t off;                   // SymDesc::off of the lane's symbol
+    int32_t bars;
+    int32_t param;
+};
+struct ReplayOut {
+    bt_summary* sum;               // [n]
+    bt_trade* trades;              // [n * trade_cap], or nullptr with trade_cap 0
+    int32_t trade_cap;
+    int64_t* equity;               // [n * pitch] or nullptr
+    int8_t* pos;                   // [n * pitch] or nullptr
+    int64_t pitch;                 // elements per curve row, >= the longest requested symbol
+};
+hipError_t launch_replay(const ReplayLane* lanes, int32_t n, const int32_t* high, const int32_t* low,
+                         const int32_t* close, const Grid& g, const ReplayOut& o, hipStream_t st);
+
 // Top-k by radix select over `key` (k_topk.hip): device-side finish into `out`.
 constexpr int kTopkCap = 2048;      // candidates sorted in LDS by the finish kernel
 constexpr int kTopkMax = 1024;      // largest k the engine accepts

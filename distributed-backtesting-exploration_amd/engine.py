@@ -42,7 +42,10 @@ TRADE_DTYPE = np.dtype([
     ("entry_px", "<i8"), ("exit_px", "<i8"),
 ])
 TOPK_DTYPE = np.dtype([("sharpe", "<f8"), ("sym", "<i4"), ("param", "<i4"), ("pnl", "<i8")])
+LANE_DTYPE = np.dtype([("sym", "<i4"), ("param", "<i4")])  # include/bt.h bt_lane
+REPLAY_MAX = 4096  # include/bt.h BT_REPLAY_MAX: lanes per Engine.replay call
 assert SUMMARY_DTYPE.itemsize == 48 and TOPK_DTYPE.itemsize == 24 and TRADE_DTYPE.itemsize == 32
+assert LANE_DTYPE.itemsize == 8
 
 
 class BtError(RuntimeError):
@@ -179,6 +182,8 @@ _LATE_SYMBOLS = {
     "bt_exchange_message_bytes": (2, [C.c_int32], C.c_int64),
     "bt_exchange_merge": (3, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                               C.c_void_p], C.c_int32),
+    "bt_replay": (3, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64], C.c_int32),
 }
 _late = {}
 
@@ -294,6 +299,37 @@ def config5_grid():
     return Grid.sma(range(5, 161, 5), range(200, 6401, 200), annualization=98280)
 
 
+def as_lanes(lanes) -> np.ndarray:
+    """The request array of Engine.replay (LANE_DTYPE[n]) from top-k records (TOPK_DTYPE: their
+    sym and param fields), an (n, 2) integer array or a list of (sym, param) pairs."""
+    a = lanes if isinstance(lanes, np.ndarray) else np.asarray(list(lanes))
+    if a.dtype.names is not None:
+        if not {"sym", "param"} <= set(a.dtype.names):
+            raise ValueError("lane records need sym and param fields")
+        a = a.reshape(-1)
+    out = np.zeros(len(a), LANE_DTYPE)
+    if a.dtype.names is not None:
+        out["sym"], out["param"] = a["sym"], a["param"]
+    elif len(a):
+        if a.ndim != 2 or a.shape[1] != 2 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("lanes: top-k records, an (n, 2) integer array or a list of (sym, param) pairs")
+        if a.min() < -2**31 or a.max() >= 2**31:
+            raise ValueError("lanes: sym and param are int32")
+        out["sym"], out["param"] = a[:, 0], a[:, 1]
+    return out
+
+
+@dataclass
+class Replay:
+    """Engine.replay's result, rows in request order."""
+    lanes: np.ndarray       # LANE_DTYPE[n], the request
+    summaries: np.ndarray   # SUMMARY_DTYPE[n]
+    n_bars: np.ndarray      # int32[n], bars of each lane's symbol
+    trades: np.ndarray | None   # TRADE_DTYPE[n, trade_cap]: the first trades, then zeros
+    equity: np.ndarray | None   # int64[n, max bars]: E_t (spec §4), zero past the symbol's bars
+    pos: np.ndarray | None      # int8[n, max bars]: position after bar t
+
+
 class Engine:
     """One engine per GPU (one process per GPU)."""
 
@@ -311,6 +347,7 @@ class Engine:
         self.trade_cap = trade_cap
         self.n_symbols = 0
         self.topk = topk
+        self._sym_bars = None  # bars by symbol id of the resident dataset, when loaded from here
 
     def close(self):
         if getattr(self, "_h", None):
@@ -327,8 +364,10 @@ class Engine:
 
     # ---- HBM-resident path
     def load_synthetic(self, seed, sym_begin, n_sym, n_bars, freq=BT_DAILY):
+        self._sym_bars = None
         _check(lib().bt_load_synthetic(self._h, seed & ((1 << 64) - 1), sym_begin, n_sym, n_bars, freq))
         self.n_symbols = n_sym
+        self._sym_bars = (sym_begin, n_sym, n_bars)
 
     def load_ohlc(self, closes, highs=None, lows=None, sym_ids=None):
         """closes: list of 1-D int arrays (ragged allowed)."""
@@ -343,9 +382,14 @@ class Engine:
         ids = np.ascontiguousarray(np.arange(len(closes), dtype=np.int64) if sym_ids is None
                                    else np.asarray(sym_ids, np.int64))
         ptr = lambda a: None if a is None else a.ctypes.data
+        self._sym_bars = None
         _check(lib().bt_load_ohlc(self._h, len(closes), ids.ctypes.data, bars.ctypes.data,
                                   offs.ctypes.data, ptr(h), ptr(lo), c.ctypes.data))
         self.n_symbols = len(closes)
+        # the engine keeps ids as int32; with a repeated id the first row wins (bt_replay)
+        self._sym_bars = {}
+        for i, b in zip(ids.astype(np.int32).tolist(), bars.tolist()):
+            self._sym_bars.setdefault(i, b)
 
     def run(self):
         _check(lib().bt_run(self._h))
@@ -402,6 +446,51 @@ class Engine:
         m = _check(lib().bt_topk_fetch_wait(self._h, slot, out.ctypes.data, k, C.byref(n)))
         return out[:m], int(n.value)
 
+    def replay(self, lanes, trade_cap: int = 0, curves: bool = False) -> Replay:
+        """Replay chosen (symbol id, param) lanes of the resident dataset on the GPU
+        (bt_replay): their full summaries, bar counts, the first trade_cap trades of each
+        (trade_cap > 0) and, with curves, the equity curve E_t and position pos_t of every bar.
+        `lanes`: top-k records (read_topk() feeds straight in), an (n, 2) integer array or a list
+        of (sym, param) pairs; at most REPLAY_MAX per call. Rows come back in request order."""
+        req = as_lanes(lanes)
+        n = len(req)
+        f = sym("bt_replay")
+        ptr = lambda a: None if a is None else a.ctypes.data
+        summ = np.zeros(max(n, 1), SUMMARY_DTYPE)
+        nb = np.zeros(max(n, 1), np.int32)
+        tr = np.zeros((max(n, 1), trade_cap), TRADE_DTYPE) if trade_cap > 0 else None
+        eq = ps = None
+        stride = 0
+        if curves:  # rows as long as the longest requested symbol
+            stride = self._replay_stride(f, req) if 0 < n <= REPLAY_MAX else 1
+            eq = np.empty((max(n, 1), stride), np.int64)
+            ps = np.empty((max(n, 1), stride), np.int8)
+        _check(f(self._h, n, req.ctypes.data if n else None, trade_cap, summ.ctypes.data,
+                 nb.ctypes.data, ptr(tr), ptr(eq), ptr(ps), stride))
+        if curves:
+            eq, ps = eq[:n], ps[:n]
+            if n == 0:
+                eq, ps = eq[:, :0], ps[:, :0]
+        return Replay(req, summ[:n], nb[:n], None if tr is None else tr[:n], eq, ps)
+
+    def _replay_stride(self, f, req) -> int:
+        """Bars of the longest requested symbol. The bar counts of a dataset loaded through this
+        object are known here; otherwise (run_batch) one replay without curves returns them."""
+        bars = self._sym_bars
+        if isinstance(bars, tuple):  # load_synthetic: ids begin .. begin + n, all of `bars` bars
+            begin, n_sym, b = bars
+            if ((req["sym"] >= begin) & (req["sym"] < begin + n_sym)).all():
+                return b
+        elif isinstance(bars, dict):
+            got = [bars.get(int(s)) for s in np.unique(req["sym"])]
+            if None not in got:
+                return max(got)
+        summ = np.zeros(len(req), SUMMARY_DTYPE)
+        nb = np.zeros(len(req), np.int32)
+        _check(f(self._h, len(req), req.ctypes.data, 0, summ.ctypes.data, nb.ctypes.data, None, None,
+                 None, 0))
+        return int(nb.max())
+
     def stats(self) -> dict:
         st = _Stats()
         _check(lib().bt_read_stats(self._h, C.byref(st)))
@@ -434,6 +523,7 @@ class Engine:
             jin[i].file = C.cast(C.c_char_p(b), C.c_void_p)
             jin[i].len = len(b)
         jout = (_JobOut * max(n, 1))()
+        self._sym_bars = None
         try:
             _check(lib().bt_run_batch(self._h, n, jin, jout))
             res = [(jout[i].status, C.string_at(jout[i].data, jout[i].len).decode()) for i in range(n)]

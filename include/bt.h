@@ -201,6 +201,38 @@ int32_t bt_topk_fetch_wait(bt_engine* e, int32_t slot, bt_topk_rec* out, int32_t
                            int64_t* n_trades);
 /* Read back the synthetic/uploaded close column of one symbol (tests). */
 int32_t bt_read_close(bt_engine* e, int32_t sym_index, int32_t* out, int32_t n);
+/* ---- replay of chosen lanes: trades, position and equity curve (k_replay.hip)
+ * Runs n (symbol, param) lanes of the dataset the engine holds (whatever the last
+ * bt_load_synthetic, bt_load_ohlc or bt_run_batch left resident; bt_run need not have been
+ * called) again, one wave per lane, and returns per lane, in request order (repeats allowed):
+ *   sum[i]      the full bt_summary, every field as bt_run produces it;
+ *   n_bars[i]   the bars of lane i's symbol;
+ *   trades      row i (trade_cap records): the first min(n_trades, trade_cap) trades, then zeros;
+ *   equity      row i (stride values): E_t of spec §4 at the close of every bar, then zeros;
+ *   pos         row i (stride values): pos_t after bar t (-1, 0, +1), then zeros.
+ * bt_lane.sym is the global symbol id of bt_topk_rec.sym, so top-k records feed straight in; with
+ * duplicate ids in the dataset the first row wins. Added within ABI 3 (additive).
+ * Synchronous: waits for the engine's streams, runs on the engine stream, copies back, returns n
+ * (0 for n == 0). It changes nothing an existing entry point reads: summaries, top-k, stats,
+ * timing counters, segments, pipeline slots and the run state are as before the call.
+ * Device staging is bounded: the lanes are processed in chunks against a fixed 256 MB budget,
+ * never n * stride, and freed by bt_engine_destroy. Any grid bt_engine_create accepts replays (the
+ * kernel keeps no window-sized state). Returns -1, with bt_last_error naming the offending value,
+ * for: a null engine, no dataset, n < 0 or n > BT_REPLAY_MAX, an unknown symbol id, param outside
+ * [0, P), trade_cap < 0, trades given with trade_cap 0 or the reverse, stride shorter than the
+ * longest requested symbol when equity or pos is given. The engine stays usable after a refusal. */
+typedef struct bt_lane {
+    int32_t sym;                      /* global symbol id (bt_topk_rec.sym) */
+    int32_t param;
+} bt_lane;
+#define BT_REPLAY_MAX 4096            /* lanes per call */
+int32_t bt_replay(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap,
+                  bt_summary* sum,    /* [n], required */
+                  int32_t* n_bars,    /* [n] or NULL */
+                  bt_trade* trades,   /* [n * trade_cap] or NULL (then trade_cap must be 0) */
+                  int64_t* equity,    /* [n * stride] or NULL */
+                  int8_t* pos,        /* [n * stride] or NULL */
+                  int64_t stride);    /* >= the longest requested symbol when equity or pos is given */
 /* Average device time of the dominant kernel (BT_FLAG_TIMING), and how many launches. */
 int32_t bt_kernel_timing(bt_engine* e, double* total_ms, int64_t* launches, const char** name);
 int32_t bt_reset_timing(bt_engine* e);
