@@ -92,9 +92,6 @@ __device__ __forceinline__ Agg dst_query_w(const Agg* D, int a, int b) {
     return agg_merge(Agg{u.x, u.y, u.z, u.w}, Agg{v.x, v.y, v.z, v.w});
 }
 
-// Upward-biased reciprocal for exact floor keys (k_sma.hip floor_key): RN(RN(1/W) * (1 + 2^-47)).
-__host__ __device__ inline double key_recip(int W) { return (1.0 / (double)W) * (1.0 + 0x1p-47); }
-
 // Identity of agg_merge: merge(kAggId, x) == x for prices in [1, 2^31) (no int32 overflow:
 // 0 - x.mn < 0 and x.mx - INT32_MAX <= 0).
 constexpr Agg kAggId = {0, 0x7FFFFFFF, 0, 0};

@@ -83,6 +83,8 @@ struct bt_engine {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     DevBuf<int32_t> d_axes[4];
+    DevBuf<int32_t> d_kwin;      // SMA: Grid::kwin, Grid::krecip
+    DevBuf<double> d_krecip;
     // dataset
     std::vector<SymDesc> syms;
     int64_t rows = 0;
@@ -249,6 +251,21 @@ void upload_grid(bt_engine* e) {
         e->d_axes[i].ensure(e->ax[i].size());
         HIPCHK(hipMemcpy(e->d_axes[i].p, e->ax[i].data(), e->ax[i].size() * 4, hipMemcpyHostToDevice));
         *dst[i] = e->d_axes[i].p;
+    }
+    e->grid.kwin = nullptr;
+    e->grid.krecip = nullptr;
+    if (e->cfg.strategy == BT_SMA_CROSS) {  // the key tasks' window table (internal.h Grid::kwin)
+        std::vector<int32_t> win(e->ax[0]);
+        win.insert(win.end(), e->ax[1].begin(), e->ax[1].end());
+        win.resize((win.size() + kKeyGrab - 1) / kKeyGrab * kKeyGrab, 1);
+        std::vector<double> recip(win.size());
+        for (size_t i = 0; i < win.size(); ++i) recip[i] = key_recip(win[i]);
+        e->d_kwin.ensure(win.size());
+        e->d_krecip.ensure(win.size());
+        HIPCHK(hipMemcpy(e->d_kwin.p, win.data(), win.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->d_krecip.p, recip.data(), recip.size() * sizeof(double), hipMemcpyHostToDevice));
+        e->grid.kwin = e->d_kwin.p;
+        e->grid.krecip = e->d_krecip.p;
     }
 }
 
@@ -943,6 +960,8 @@ void bt_engine_destroy(bt_engine* e) {
             (void)hipEventDestroy(ev.second);
         }
         for (auto& b : e->d_axes) b.release();
+        e->d_kwin.release();
+        e->d_krecip.release();
         e->d_syms.release();
         e->d_c.release();
         e->d_h.release();

@@ -53,7 +53,13 @@ struct Grid {
     const int32_t* b;
     const int32_t* c;
     const int32_t* d;
+    // SMA key tasks (k_sma.hip stage_keys): the window lengths, fast rows then slow rows, padded
+    // with length 1 to a whole kKeyGrab group, and their biased reciprocals key_recip(W). Read
+    // with wave-uniform indices, so a group's values arrive in scalar registers.
+    const int32_t* kwin;
+    const double* krecip;
 };
+constexpr int kKeyGrab = 4;        // SMA windows per key task (one LDS atomic per group)
 
 // Outputs of one run (device pointers).
 struct Out {
@@ -208,6 +214,10 @@ bool engine_exchange_view(bt_engine* e, ExchangeView& v, std::string& err);
 void engine_exchange_enqueued(bt_engine* e);
 
 // Shared host/device helpers.
+// Upward-biased reciprocal for exact floor keys (k_sma.hip floor_key): RN(RN(1/W) * (1 + 2^-47)),
+// two correctly rounded IEEE operations on the host as on the device.
+__host__ __device__ inline double key_recip(int W) { return (1.0 / (double)W) * (1.0 + 0x1p-47); }
+
 __host__ __device__ inline uint64_t order_key(double x) {
     union { double d; uint64_t u; } v;
     v.d = x;

@@ -37,25 +37,23 @@ namespace {
 constexpr int kKS = kTile + 4;        // int32 key row stride: rows 16-B aligned for b128 reads
 constexpr int kStages = 3;            // tile buffers in flight (cT, Q)
 constexpr int kDstStages = 2;         // drawdown tables: built in interval k - 1, read in k
-constexpr int kKeyGrab = 4;           // windows per key task (one LDS atomic per group)
+constexpr int kRingMirror = kTile;    // ring entries repeated past its end (ring_store)
 // Key-row pairs in flight in the 16-wave (ONE_TRIP) compare: 2, 4, 8 and 16 are within 0.5 %
 // of each other on config 5's shard (round 4); the whole 10,000-symbol workload ran 3 % slower
 // with 16 and no VGPR cap, so 2.
 constexpr int kCmpDepth1 = 2;
 
 struct SmaLds {                       // byte offsets into dynamic LDS
-    size_t ring, keys, invw, win, dst, ct, ql, nar, ctr, total;
+    size_t ring, keys, dst, ct, ql, nar, ctr, total;
 };
 
 __host__ __device__ inline SmaLds sma_lds_layout(int ring, int nw) {
     SmaLds L;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 15) & ~size_t(15); return r; };
-    L.ring = take((size_t)ring * 8);
+    L.ring = take((size_t)(ring + kRingMirror) * 8);
     const int nwp = (nw + kKeyGrab - 1) / kKeyGrab * kKeyGrab;  // key rows: whole groups
     L.keys = take((size_t)2 * nwp * kKS * 4);
-    L.invw = take((size_t)nwp * 8);
-    L.win = take((size_t)nwp * 4);
     L.dst = take((size_t)kDstStages * kDstLevels * kTile * sizeof(Agg));
     L.ct = take((size_t)kStages * kTile * 4);
     L.ql = take((size_t)kStages * 2 * kTile * 8);
@@ -77,6 +75,20 @@ __device__ __forceinline__ int32_t load_close(const int32_t* __restrict__ crow, 
     return t < B ? crow[t] : 0;
 }
 
+// Appends the prefix sums of tile t0 (v = sum of closes through bar t0 + lane) to the ring. The
+// ring's first kRingMirror entries are kept a second time past its end, ring[R + i] == ring[i],
+// so that 64 consecutive entries from any start below R are read without a wrap (stage_keys).
+// Only the tiles at the ring's start (entries 1..63) and end (entry R, i.e. 0) touch them: a
+// wave-uniform test skips the lane-masked second store in the others.
+__device__ __forceinline__ void ring_store(double* ring, int R, int t0, int lane, double v) {
+    const int i = (t0 + lane + 1) & (R - 1);
+    ring[i] = v;
+    const int rb = t0 & (R - 1);
+    if (rb == 0 || rb == R - kTile) {
+        if (i < kRingMirror) ring[R + i] = v;
+    }
+}
+
 // c = close of bar t0 + lane (0 past the end), loaded one tile ahead by the caller so the HBM
 // latency is off the pipeline's critical path. The tile's drawdown table is a stage-2 task
 // (stage_keys), built from the closes stored here.
@@ -89,7 +101,7 @@ __device__ __forceinline__ void stage_ring(int32_t c, int B, int t0, int lane, i
     const int32_t cp = (int32_t)__builtin_amdgcn_update_dpp((uint32_t)cy.prevc, (uint32_t)c,
                                                             0x138, 0xf, 0xf, false);
     const int64_t inc = wave_iscan_i64((int64_t)c);
-    ring[(t + 1) & (R - 1)] = (double)(cy.P + inc);
+    ring_store(ring, R, t0, lane, (double)(cy.P + inc));
     cT[lane] = c;
     int64_t q = 0, q2 = 0;
     uint32_t dv = 0;  // |c_t - c_(t-1)| (prices in [1, 2^31): the difference fits int32)
@@ -118,6 +130,12 @@ __device__ __forceinline__ void stage_ring(int32_t c, int B, int t0, int lane, i
 // per wave (the barrier separates rounds). The next group's atomic is in flight while the
 // current group computes (its result is read only at the end of the iteration), and the group's
 // ring reads are issued together.
+// A group's four lengths and reciprocals come from the engine's tables in global memory
+// (Grid::kwin, Grid::krecip) at a wave-uniform index: scalar loads into SGPRs, issued as soon as
+// the group is known (the end of the previous iteration), so the wait at the top of the
+// iteration, which the grab's atomic shares, covers them. A window's 64 ring entries start at
+// the scalar offset (t0 + 1 - W) & (R - 1) and, thanks to the ring's mirror (ring_store), never
+// wrap: one add of that offset to the lane's own address per window, no per-lane mask.
 // Bars without a full window (or past the series end) get key -1 on fast rows and -2 on slow
 // rows: their difference is never 0, so they never look like ties to the compare stage (they
 // are outside every lane's decision mask anyway).
@@ -145,62 +163,76 @@ __host__ __device__ inline uint32_t key_round_len(int nwp, int nwaves) {
     return (uint32_t)kKeyGrab * ((uint32_t)nwp / kKeyGrab + 1 + (uint32_t)nwaves);
 }
 
+struct KeyGroup {                     // one key task's windows, wave-uniform
+    int32_t W[kKeyGrab];
+    double I[kKeyGrab];
+};
+// Counter value w of a round -> its group; the table task and a failing grab read a valid group
+// that nobody uses (the clamp is scalar). The tables are written by the host before the launch
+// and never by a kernel: read through the constant address space, whose loads at a uniform
+// address are scalar loads whatever else the kernel stores.
+typedef __attribute__((address_space(4))) const int32_t const_i32;
+typedef __attribute__((address_space(4))) const double const_f64;
+__device__ __forceinline__ KeyGroup key_group(const int32_t* kwin, const double* krecip,
+                                              uint32_t w, int nwp) {
+    const uint32_t i = min(w - (uint32_t)kKeyGrab, (uint32_t)(nwp - kKeyGrab));
+    const_i32* cw = (const_i32*)kwin + i;
+    const_f64* cr = (const_f64*)krecip + i;
+    KeyGroup g;
+#pragma unroll
+    for (int q = 0; q < kKeyGrab; ++q) {
+        g.W[q] = cw[q];
+        g.I[q] = cr[q];
+    }
+    return g;
+}
+
 // Stage 2 of round r (tile r): the tile's drawdown table (device_common.h dst_build) from the
 // closes stage 1 left in LDS (cTr), into Dr, as the round's first task, then the key groups.
 // The table is a task rather than a fixed role: on the half-empty seventh parameter wave of a
 // config-2 block it set the tile (that wave's compare and walk plus the table's DPP chain).
-__device__ __forceinline__ void stage_keys(int t0, int B, int nw, int nwp, int nf, int wmax, int R,
-                                           double* ring, const int32_t* win,
-                                           const double* invw, int32_t* K, uint32_t* ctr,
-                                           uint32_t round, int nwaves, int lane,
+__device__ __forceinline__ void stage_keys(int t0, int B, int nwp, int nf, int wmax, int R,
+                                           const double* ring, const int32_t* __restrict__ kwin,
+                                           const double* __restrict__ krecip, int32_t* K,
+                                           uint32_t* ctr, uint32_t round, int nwaves, int lane,
                                            const int32_t* cTr, Agg* Dr) {
     const int t = t0 + lane;
-    const double top = ring[(t + 1) & (R - 1)];
+    const double* ringl = ring + lane;  // + a scalar start: entries start .. start + 63
+    const double top = ringl[(t0 + 1) & (R - 1)];
     // wave-uniform: every bar of the tile has a full window for every window length
     const bool full = t0 + 1 - wmax >= 0 && t0 + kTile <= B;
     const uint32_t base = round * key_round_len(nwp, nwaves);
     uint32_t w = __builtin_amdgcn_readlane(grab_issue(ctr, lane), 0) - base;
+    KeyGroup gw = key_group(kwin, krecip, w, nwp);
 #pragma unroll 1
     while (w < (uint32_t)(nwp + kKeyGrab)) {
         const uint32_t vn = grab_issue(ctr, lane);  // next group, read at the end
         if (w == 0) {  // the table task (counter value 0 of the round)
             dst_build<true>(cTr[lane], lane, Dr);
             w = __builtin_amdgcn_readlane(vn, 0) - base;
+            gw = key_group(kwin, krecip, w, nwp);
             continue;
         }
         w -= kKeyGrab;
-        // w is a multiple of kKeyGrab: the group's lengths and reciprocals are aligned 16-B
-        // reads; rows nw..nwp-1 are padding (length 1) whose keys nobody reads
-        int Wv[kKeyGrab];
-        double Iv[kKeyGrab], Fv[kKeyGrab];
-#pragma unroll
-        for (int q = 0; q < kKeyGrab; q += 4) {
-            const int4 W4 = *reinterpret_cast<const int4*>(win + w + q);
-            Wv[q] = W4.x; Wv[q + 1] = W4.y; Wv[q + 2] = W4.z; Wv[q + 3] = W4.w;
-        }
-#pragma unroll
-        for (int q = 0; q < kKeyGrab; q += 2) {
-            const double2 I2 = *reinterpret_cast<const double2*>(invw + w + q);
-            Iv[q] = I2.x; Iv[q + 1] = I2.y;
-        }
+        // rows nw..nwp-1 are padding (length 1) whose keys nobody reads
+        int32_t kq[kKeyGrab];
 #pragma unroll
         for (int q = 0; q < kKeyGrab; ++q) {
-            Wv[q] = __builtin_amdgcn_readfirstlane(Wv[q]);
-            Fv[q] = top - ring[(t + 1 - Wv[q]) & (R - 1)];  // exact (< 2^53)
+            const double F = top - ringl[(t0 + 1 - gw.W[q]) & (R - 1)];  // exact (< 2^53)
+            kq[q] = floor_key(F, gw.I[q]);
         }
         int32_t* Kw = K + w * kKS + lane;
         if (full) {
 #pragma unroll
-            for (int q = 0; q < kKeyGrab; ++q) Kw[q * kKS] = floor_key(Fv[q], Iv[q]);
+            for (int q = 0; q < kKeyGrab; ++q) Kw[q * kKS] = kq[q];
         } else {
             const bool tin = t < B;
 #pragma unroll
-            for (int q = 0; q < kKeyGrab; ++q) {
-                const int32_t kq = floor_key(Fv[q], Iv[q]);
-                Kw[q * kKS] = (tin && t + 1 - Wv[q] >= 0) ? kq : ((int)(w + q) < nf ? -1 : -2);
-            }
+            for (int q = 0; q < kKeyGrab; ++q)
+                Kw[q * kKS] = (tin && t + 1 - gw.W[q] >= 0) ? kq[q] : ((int)(w + q) < nf ? -1 : -2);
         }
         w = __builtin_amdgcn_readlane(vn, 0) - base;
+        gw = key_group(kwin, krecip, w, nwp);
     }
 }
 
@@ -413,8 +445,6 @@ __device__ __forceinline__ void sma_body(const SymDesc* __restrict__ syms,
     const SmaLds LL = sma_lds_layout(R, nw);
     double* ring = reinterpret_cast<double*>(smem + LL.ring);
     int32_t* keys = reinterpret_cast<int32_t*>(smem + LL.keys);
-    double* invw = reinterpret_cast<double*>(smem + LL.invw);
-    int32_t* win = reinterpret_cast<int32_t*>(smem + LL.win);
     Agg* dst = reinterpret_cast<Agg*>(smem + LL.dst);
     int32_t* cts = reinterpret_cast<int32_t*>(smem + LL.ct);
     int64_t* qls = reinterpret_cast<int64_t*>(smem + LL.ql);
@@ -465,19 +495,25 @@ __device__ __forceinline__ void sma_body(const SymDesc* __restrict__ syms,
 
     const int nwp = (nw + kKeyGrab - 1) / kKeyGrab * kKeyGrab;
     const uint32_t key_round = key_round_len(nwp, nwaves);
-    for (int w = tid; w < nwp; w += blockDim.x) {
-        const int W = w < nf ? g.a[w] : (w < nw ? g.b[w - nf] : 1);
-        win[w] = W;
-        invw[w] = key_recip(W);
-    }
     if (tid == 0) {
-        ring[(T_scan * kTile) & (R - 1)] = 0.0;  // prefix base: sums over scanned bars
+        const int i0 = (T_scan * kTile) & (R - 1);
+        ring[i0] = 0.0;                          // prefix base: sums over scanned bars
+        if (i0 == 0) ring[R] = 0.0;              // its mirror (ring_store)
         *ctr = (uint32_t)T_walk * key_round;     // key rounds are numbered by tile
     }
     __syncthreads();
-    const int warm = max(win[kf], win[ks]) - 1;  // first decision bar of this lane
+    const int32_t wf = g.kwin[kf], ws = g.kwin[ks];
+    const int warm = max(wf, ws) - 1;  // first decision bar of this lane
     // both window lengths in one register (each < 2^16), for the rare exact tie settle
-    const uint32_t fsw = (uint32_t)win[kf] | ((uint32_t)win[ks] << 16);
+    const uint32_t fsw = (uint32_t)wf | ((uint32_t)ws << 16);
+    // the wave's first tile with a decision bar: before it every lane is flat with an empty
+    // decision mask (F = 0, the accounts do not move), so stage 3 is skipped whole; a wave
+    // without an active lane never runs it. The key rows are computed all the same (their
+    // sentinels keep unset rows from looking like ties later).
+    int wmin = active ? warm : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wmin = min(wmin, __shfl_xor(wmin, o));
+    const int kfirst = __builtin_amdgcn_readfirstlane(wmin) >> 6;
 
     ScanCarry cy{0, (T_scan > 0 && T_scan * kTile - 1 < B) ? crow[T_scan * kTile - 1] : 0};
     // SEG lookback: the prefix ring over the windows before the first walked bar (config 5: 100
@@ -503,6 +539,9 @@ __device__ __forceinline__ void sma_body(const SymDesc* __restrict__ syms,
                 }
             }
         }
+        // nobody reads the ring before the lookback ends: its mirror (ring_store) in one copy
+        // by this wave, instead of a test per tile in the loop
+        ring[R + lane] = ring[lane];
     }
     // prologue: stage 1 for the first two walked tiles; stage 2 for the first. The helper keeps
     // the closes of the tile after next in flight (cpre) across the barrier.
@@ -520,7 +559,7 @@ __device__ __forceinline__ void sma_body(const SymDesc* __restrict__ syms,
         __syncthreads();
     }
     if (T_walk < T_end)
-        stage_keys(T_walk * kTile, B, nw, nwp, nf, g.wmax, R, ring, win, invw,
+        stage_keys(T_walk * kTile, B, nwp, nf, g.wmax, R, ring, g.kwin, g.krecip,
                    keys + (T_walk & 1) * nwp * kKS, ctr, (uint32_t)T_walk, nwaves, lane,
                    cts + (T_walk % kStages) * kTile, dst + (T_walk % kDstStages) * kDstLevels * kTile);
     __syncthreads();
@@ -606,7 +645,7 @@ __device__ __forceinline__ void sma_body(const SymDesc* __restrict__ syms,
         BT_STAMP(0)
         // ---- stage 3 (tile k)
         if (SEG && active && k == T_acct && k != T_walk) enter_acct();
-        if (active) {
+        if (active && k >= kfirst) {
             // blocks of more than 8 waves (one per CU): compare and walk at raised priority over
             // the keys / scan work of other waves (config 5 156.4 -> 151.0 ms; config 2's 8-wave
             // blocks are ~1 % slower with it)
@@ -724,7 +763,7 @@ __device__ __forceinline__ void sma_body(const SymDesc* __restrict__ syms,
             if (ONE_TRIP) __builtin_amdgcn_s_setprio(0);
         }
         if (k + 1 < T_end && !BT_ABL(g, 2))
-            stage_keys(t0 + kTile, B, nw, nwp, nf, g.wmax, R, ring, win, invw, keys + ((k + 1) & 1) * nwp * kKS,
+            stage_keys(t0 + kTile, B, nwp, nf, g.wmax, R, ring, g.kwin, g.krecip, keys + ((k + 1) & 1) * nwp * kKS,
                        ctr, (uint32_t)(k + 1), nwaves, lane, cts + ((k + 1) % kStages) * kTile,
                        dst + ((k + 1) % kDstStages) * kDstLevels * kTile);
         BT_STAMP(1)
