@@ -23,6 +23,7 @@
 
 #include "csv.h"
 #include "internal.h"
+#include "plan.h"
 
 using namespace bt;
 
@@ -63,12 +64,6 @@ struct DevBuf {
     }
 };
 
-uint32_t next_pow2(uint32_t x) {
-    uint32_t r = 1;
-    while (r < x) r <<= 1;
-    return r;
-}
-
 }  // namespace
 
 void bt::set_last_error(const std::string& s) { set_err(s); }
@@ -104,10 +99,11 @@ struct bt_engine {
     int64_t nrun = 0;
     DevBuf<bt_sums> d_sums;
     DevBuf<bt_trade> d_trades;
-    // Bollinger bar segments (k_tile.hip): requested count (0 = auto, 1 = off), burn-in tiles,
-    // the records of a split run and the count the last run used
-    int32_t seg_req = 0, seg_burn = kDefaultBurnTiles, seg_last = 1;
-    bool seg_burn_set = false;
+    int cus = kCusFallback;      // compute units of the device (launch plans, plan.h)
+    int32_t max_bars = 0;        // bars of the longest symbol
+    // bar segments: requested count (0 = auto, 1 = off) and burn-in tiles (0 = the strategy's
+    // default), the records of a split run and the count the last run used
+    int32_t seg_req = 0, burn_req = 0, seg_last = 1;
     DevBuf<SegRec> d_seg;
     DevBuf<double> d_segema;
     DevBuf<unsigned long long> d_refixed;
@@ -161,81 +157,12 @@ const char* kernel_name(int32_t strategy) {
 }
 
 std::string validate_and_copy(bt_engine* e, const bt_config& c) {
-    auto copy_axis = [&](int slot, const int32_t* src, int32_t n, const char* what, int32_t lo,
-                         int32_t hi) -> std::string {
-        if (n <= 0 || src == nullptr) return std::string("empty axis: ") + what;
-        e->ax[slot].assign(src, src + n);
-        for (int32_t v : e->ax[slot])
-            if (v < lo || v > hi)
-                return std::string("value out of range on axis ") + what + ": " + std::to_string(v);
-        return "";
-    };
-    std::string err;
-    e->grid.strategy = c.strategy;
-    switch (c.strategy) {
-        case BT_SMA_CROSS: {
-            if (!(err = copy_axis(0, c.fast, c.n_fast, "fast", 1, kMaxBars)).empty()) return err;
-            if (!(err = copy_axis(1, c.slow, c.n_slow, "slow", 1, kMaxBars)).empty()) return err;
-            const int64_t mf = *std::max_element(e->ax[0].begin(), e->ax[0].end());
-            const int64_t ms = *std::max_element(e->ax[1].begin(), e->ax[1].end());
-            e->grid.na = c.n_fast;
-            e->grid.nb = c.n_slow;
-            e->grid.nc = e->grid.nd = 1;
-            e->grid.wmax = (int32_t)std::max(mf, ms);
-            // prefix ring: windows + three tiles in flight (k_sma.hip pipeline)
-            e->grid.ring = (int32_t)next_pow2((uint32_t)e->grid.wmax + 3 * kTile);
-            const size_t lds = sma_lds_bytes(e->grid);
-            if (lds > 160 * 1024) return "SMA grid needs more LDS than a CU has (windows too long)";
-            break;
-        }
-        case BT_EMA_OLS: {
-            if (!(err = copy_axis(0, c.span, c.n_span, "span", 1, kMaxBars)).empty()) return err;
-            if (!(err = copy_axis(1, c.ols, c.n_ols, "ols", 1, 1 << 16)).empty()) return err;
-            if (c.band_bps < 0 || c.band_bps >= 10000) return "band_bps out of range";
-            if (c.n_span > 64) return "EMA grid: at most 64 spans (one helper lane per span)";
-            e->grid.na = c.n_span;
-            e->grid.nb = c.n_ols;
-            e->grid.nc = e->grid.nd = 1;
-            e->grid.band_bps = c.band_bps;
-            e->grid.wmax = *std::max_element(e->ax[1].begin(), e->ax[1].end());
-            // prefix ring, a multiple of the tile (k_tile.hip): a window back from the stage
-            // being flagged, which ends two 128-bar stages before the last scanned bar
-            e->grid.ring = (e->grid.wmax + 5 * kTile - 1) / kTile * kTile;
-            if (ema_lds_bytes(e->grid, 1) > 160 * 1024) return "EMA grid needs more LDS than a CU has (OLS windows too long)";
-            break;
-        }
-        case BT_BOLL: {
-            if (!(err = copy_axis(0, c.bwin, c.n_bwin, "bwin", 1, 1 << 16)).empty()) return err;
-            if (!(err = copy_axis(1, c.k_num, c.n_k, "k_num", 0, 1 << 20)).empty()) return err;
-            if (!(err = copy_axis(2, c.sl_bps, c.n_sl, "sl_bps", 0, 9999)).empty()) return err;
-            if (!(err = copy_axis(3, c.tp_bps, c.n_tp, "tp_bps", 0, 9999)).empty()) return err;
-            if (c.k_den < 1 || c.k_den > (1 << 20)) return "k_den out of range";
-            e->grid.na = c.n_bwin;
-            e->grid.nb = c.n_k;
-            e->grid.nc = c.n_sl;
-            e->grid.nd = c.n_tp;
-            e->grid.k_den = c.k_den;
-            e->grid.wmax = *std::max_element(e->ax[0].begin(), e->ax[0].end());
-            // z tests D^2 kd^2 vs kn^2 Q with D^2, Q < w^2 2^62: exact in int128 while
-            // w * max(k_num, k_den) < 2^32 (spec §4, oracle/oracle.c orc_boll)
-            const int64_t kmax = std::max<int64_t>(c.k_den, *std::max_element(e->ax[1].begin(), e->ax[1].end()));
-            if ((int64_t)e->grid.wmax * kmax >= (1LL << 32)) return "Bollinger grid outside the exact int128 range (window * k >= 2^32)";
-            e->grid.ring = (e->grid.wmax + 4 * kTile - 1) / kTile * kTile;
-            for (int q = 0; q < 8; ++q) {
-                const int64_t kn = q < c.n_k ? e->ax[1][q] : 0;
-                e->grid.kn2[q] = (double)(kn * kn);  // exact: kn <= 2^20
-            }
-            e->grid.kmin_idx = (int32_t)(std::min_element(e->ax[1].begin(), e->ax[1].end()) - e->ax[1].begin());
-            if (boll_lds_bytes(e->grid) > 160 * 1024) return "Bollinger grid needs more LDS than a CU has (windows too long)";
-            break;
-        }
-        default:
-            return "unknown strategy";
-    }
-    const int64_t P = (int64_t)e->grid.na * e->grid.nb * e->grid.nc * e->grid.nd;
-    if (P <= 0 || P > (1 << 20)) return "parameter grid too large";
-    e->P = (int32_t)P;
-    e->grid.n_params = e->P;
+    const std::string err = plan_grid(c, e->grid);
+    if (!err.empty()) return err;
+    AxisSpec ax[4];
+    const int nax = config_axes(c, ax);
+    for (int i = 0; i < nax; ++i) e->ax[i].assign(ax[i].v, ax[i].v + ax[i].n);
+    e->P = e->grid.n_params;
     if (c.annualization <= 0) return "annualization must be positive";
     e->grid.sqrt_ann = std::sqrt((double)c.annualization);
     if (c.topk < 0 || c.topk > kTopkMax) return "topk must be in [0, 1024]";
@@ -282,6 +209,8 @@ void set_dataset(bt_engine* e, std::vector<SymDesc>&& syms, int64_t rows) {
     sync_all(e);
     e->syms = std::move(syms);
     e->rows = rows;
+    e->max_bars = 0;
+    for (const SymDesc& sd : e->syms) e->max_bars = std::max(e->max_bars, sd.bars);
     const size_t n_sym = e->syms.size();
     e->d_syms.ensure(std::max<size_t>(1, n_sym));
     if (n_sym)
@@ -396,72 +325,34 @@ void run_impl(bt_engine* e) {
         }
         HIPCHK(hipEventRecord(ev.first, e->stream));
     }
-    hipError_t err = hipSuccess;
+    const LaunchPlan pl = plan_launch(e->grid, e->ax[0].data(),
+                                      RunShape{S, e->max_bars, parity, e->seg_req, e->burn_req, e->cus});
+    SegArgs sg{nullptr, nullptr, nullptr, nullptr, pl.G, pl.burn_tiles};
+    if (pl.G > 1) {
+        e->d_seg.ensure(pl.seg_slots);
+        sg.rec = e->d_seg.p;
+        if (pl.pos_bytes) sg.pos = reinterpret_cast<int8_t*>(e->d_seg.p) + pl.pos_off;
+        if (pl.ema_doubles) {
+            e->d_segema.ensure(pl.ema_doubles);
+            sg.ema = e->d_segema.p;
+        }
+        e->d_refixed.ensure(1);
+        HIPCHK(hipMemsetAsync(e->d_refixed.p, 0, sizeof(unsigned long long), e->stream));
+        sg.refixed = e->d_refixed.p;
+    }
+    e->seg_last = pl.G;
+    hipError_t err;
     switch (e->cfg.strategy) {
-        case BT_SMA_CROSS: {
-            // bar segments (k_sma.hip) for shards of few, long one-block-per-CU symbols
-            SegArgs sg{nullptr, nullptr, nullptr, nullptr, 1, e->seg_burn_set ? e->seg_burn : kSmaBurnTiles};
-            if (!parity) {
-                int32_t maxb = 0;
-                for (const SymDesc& sd : e->syms) maxb = std::max(maxb, sd.bars);
-                sg.G = e->seg_req > 0 ? e->seg_req
-                                      : sma_auto_segments(S, e->P, maxb, e->grid.wmax, sg.burn_tiles);
-            }
-            if (sg.G > 1) {
-                // one SegRec slot per SmaSegRec, then the int8 start / end position planes
-                const size_t nrec = (size_t)sg.G * S * e->P;
-                e->d_seg.ensure(nrec + (2 * nrec + sizeof(SegRec) - 1) / sizeof(SegRec));
-                sg.pos = reinterpret_cast<int8_t*>(e->d_seg.p + nrec);
-                e->d_refixed.ensure(1);
-                HIPCHK(hipMemsetAsync(e->d_refixed.p, 0, sizeof(unsigned long long), e->stream));
-                sg.rec = e->d_seg.p;
-                sg.refixed = e->d_refixed.p;
-            }
-            e->seg_last = sg.G;
-            err = launch_sma(e->d_syms.p, S, e->d_c.p, e->grid, out, parity, sg, e->stream);
+        case BT_SMA_CROSS:
+            err = launch_sma(e->d_syms.p, S, e->d_c.p, e->grid, out, parity, sg, pl, e->stream);
             break;
-        }
-        case BT_EMA_OLS: {
-            int32_t maxspan = 1, maxb = 0;
-            for (int32_t v : e->ax[0]) maxspan = std::max(maxspan, v);
-            for (const SymDesc& sd : e->syms) maxb = std::max(maxb, sd.bars);
-            // the default burn-in lets every span's chain meet the true one; an explicit one
-            // (bt_set_segments) is honoured, the fix pass covering a short one
-            const int32_t burn = e->seg_burn_set ? e->seg_burn : ema_burn_tiles(maxspan);
-            SegArgs sg{nullptr, nullptr, nullptr, nullptr, 1, burn};
-            if (!parity) sg.G = e->seg_req > 0 ? e->seg_req : ema_auto_segments(S, e->P, maxb, burn);
-            if (sg.G > 1) {
-                e->d_seg.ensure((size_t)sg.G * S * e->P);
-                e->d_segema.ensure((size_t)sg.G * S * kEmaSegStride);
-                e->d_refixed.ensure(1);
-                HIPCHK(hipMemsetAsync(e->d_refixed.p, 0, sizeof(unsigned long long), e->stream));
-                sg.rec = e->d_seg.p;
-                sg.refixed = e->d_refixed.p;
-                sg.ema = e->d_segema.p;
-            }
-            e->seg_last = sg.G;
-            err = launch_ema_ols(e->d_syms.p, S, e->d_c.p, e->grid, out, parity, sg, e->stream);
+        case BT_EMA_OLS:
+            err = launch_ema_ols(e->d_syms.p, S, e->d_c.p, e->grid, out, parity, sg, pl, e->stream);
             break;
-        }
-        case BT_BOLL: {
-            SegArgs sg{nullptr, nullptr, nullptr, nullptr, 1, e->seg_burn};
-            if (!parity) {
-                int32_t maxb = 0;
-                for (const SymDesc& sd : e->syms) maxb = std::max(maxb, sd.bars);
-                sg.G = e->seg_req > 0 ? e->seg_req : boll_auto_segments(S, e->P, maxb);
-            }
-            if (sg.G > 1) {
-                e->d_seg.ensure((size_t)sg.G * S * e->P);
-                e->d_refixed.ensure(1);
-                HIPCHK(hipMemsetAsync(e->d_refixed.p, 0, sizeof(unsigned long long), e->stream));
-                sg.rec = e->d_seg.p;
-                sg.refixed = e->d_refixed.p;
-            }
-            e->seg_last = sg.G;
-            err = launch_boll(e->d_syms.p, S, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, out, parity,
-                              sg, e->stream);
+        default:
+            err = launch_boll(e->d_syms.p, S, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, out, parity, sg, pl,
+                              e->stream);
             break;
-        }
     }
     HIPCHK(err);
     if (timing) {
@@ -473,11 +364,8 @@ void run_impl(bt_engine* e) {
         // marker less between two runs' kernels)
         if (!timing) HIPCHK(hipEventRecord(e->ev_kdone, e->stream));
         HIPCHK(hipStreamWaitEvent(e->tstream, timing ? ev.second : e->ev_kdone, 0));
-        // the chain's histograms take no LDS beside a strategy kernel whose blocks fill a CU's
-        // (EMA+OLS in 128-bar stages: k_topk.hip topk_hist_global)
-        const bool lds_free = e->grid.strategy == BT_EMA_OLS && ema_stage_tiles(e->grid) == 2;
         HIPCHK(launch_topk(e->d_key[b].p, e->d_sum[b].p, e->d_syms.p, (int64_t)S * e->P, e->P,
-                           e->cfg.topk, topk_work(e), e->tstream, lds_free));
+                           e->cfg.topk, topk_work(e), e->tstream, pl.topk_lds_free));
         HIPCHK(hipEventRecord(e->ev_tdone[b], e->tstream));
         e->tdone_armed[b] = true;
     }
@@ -922,6 +810,9 @@ bt_engine* bt_engine_create(const bt_config* cfg, char* err, size_t errlen) {
             throw HipFail{"HIP device " + std::to_string(cfg->device) + " not present (" +
                           std::to_string(ndev) + " visible)"};
         activate(e);
+        if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess ||
+            e->cus <= 0)
+            e->cus = kCusFallback;
         if (cfg->stream) {
             e->stream = (hipStream_t)cfg->stream;
         } else {
@@ -1018,8 +909,7 @@ int32_t bt_set_segments(bt_engine* e, int32_t segments, int32_t burn_tiles) {
     ABI_GUARD(-1, {
         if (!e || segments < 0 || segments > 64 || burn_tiles < 0) throw HipFail{"bad arguments"};
         e->seg_req = segments;
-        e->seg_burn = burn_tiles > 0 ? burn_tiles : kDefaultBurnTiles;
-        e->seg_burn_set = burn_tiles > 0;
+        e->burn_req = burn_tiles;
         return 0;
     })
 }

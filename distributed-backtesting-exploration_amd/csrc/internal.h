@@ -42,7 +42,7 @@ struct Grid {
     int32_t band_bps, k_den;
     int32_t wmax;                  // largest window of the grid (prefix ring sizing)
     int32_t ring;                  // prefix ring length >= wmax + 3 kTile (SMA: a power of two;
-                                   // tile kernels: a multiple of kTile)
+                                   // tile kernels: a multiple of kTile; plan.cpp plan_grid)
     double sqrt_ann;               // sqrt((double)annualization), computed on the host
     double kn2[8];                 // Bollinger: k_num^2 of the first 8 k values (kernel arguments,
                                    // so the z tests read them from scalar registers)
@@ -128,40 +128,21 @@ struct SegArgs {
     int32_t G;                     // segments per symbol (1 = no split)
     int32_t burn_tiles;            // tiles walked before a speculative segment's first bar
 };
-constexpr int kDefaultBurnTiles = 64;
 constexpr int kEmaSegStride = 128;  // doubles per (segment, symbol) in SegArgs::ema
-// Launchers (k_*.hip). All enqueue on `st` and return hipError_t.
+// Launchers (k_*.hip). All enqueue on `st` and return hipError_t. The strategy launchers enqueue
+// what the run's LaunchPlan (plan.h) says: they decide nothing themselves.
+struct LaunchPlan;
 hipError_t launch_gen(const SymDesc* syms, int32_t n_sym, uint64_t seed, int32_t freq,
                       int32_t* o, int32_t* h, int32_t* l, int32_t* c, hipStream_t st);
-size_t sma_lds_bytes(const Grid& g);  // dynamic LDS of the SMA kernel for this grid
-struct SmaShape {                     // SMA launch shape for P parameters (k_sma.hip)
-    int pw;                           // parameter waves per block
-    int dedicated;                    // 1: an extra helper wave runs the tile scan
-    int block, gy;                    // threads per block, y-blocks per symbol
-};
-SmaShape sma_shape(int P);
 hipError_t launch_sma(const SymDesc* syms, int32_t n_sym, const int32_t* close, const Grid& g,
-                      const Out& out, bool parity, const SegArgs& seg, hipStream_t st);
-// SMA segments for this shard (auto mode) and the default burn-in (k_sma.hip)
-int32_t sma_auto_segments(int32_t n_sym, int32_t n_params, int32_t max_bars, int32_t wmax,
-                          int32_t burn_tiles);
-constexpr int kSmaBurnTiles = 2;
-int device_cus();  // compute units of the current device
-// dynamic LDS of the EMA+OLS tile kernel with ts tiles per stage, and the ts an unsplit launch uses
-size_t ema_lds_bytes(const Grid& g, int ts);
-int ema_stage_tiles(const Grid& g);
-size_t boll_lds_bytes(const Grid& g);  // dynamic LDS of the Bollinger tile kernel
+                      const Out& out, bool parity, const SegArgs& seg, const LaunchPlan& pl,
+                      hipStream_t st);
 hipError_t launch_ema_ols(const SymDesc* syms, int32_t n_sym, const int32_t* close, const Grid& g,
-                          const Out& out, bool parity, const SegArgs& seg, hipStream_t st);
-// EMA+OLS segments: count for this shard (auto mode) and the burn-in a speculative segment needs
-// for every span's fp64 chain to meet the true one bit for bit (~16 spans of bars measured).
-int32_t ema_auto_segments(int32_t n_sym, int32_t n_params, int32_t max_bars, int32_t burn_tiles);
-int32_t ema_burn_tiles(int32_t max_span);
+                          const Out& out, bool parity, const SegArgs& seg, const LaunchPlan& pl,
+                          hipStream_t st);
 hipError_t launch_boll(const SymDesc* syms, int32_t n_sym, const int32_t* high, const int32_t* low,
                        const int32_t* close, const Grid& g, const Out& out, bool parity,
-                       const SegArgs& seg, hipStream_t st);
-// Segments per symbol the Bollinger launcher would choose for this shard (auto mode).
-int32_t boll_auto_segments(int32_t n_sym, int32_t n_params, int32_t max_bars);
+                       const SegArgs& seg, const LaunchPlan& pl, hipStream_t st);
 
 // Replay of chosen lanes (k_replay.hip, bt_replay): one wave64 workgroup per request, which walks
 // the symbol's rows and writes its summary, its first trade_cap trades and, when asked, E_t and

@@ -28,40 +28,18 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "lds_layout.h"
+#include "plan.h"
 #include "tile_common.h"
 
 namespace bt {
 
 namespace {
 
-constexpr int kKS = kTile + 4;        // int32 key row stride: rows 16-B aligned for b128 reads
-constexpr int kStages = 3;            // tile buffers in flight (cT, Q)
-constexpr int kDstStages = 2;         // drawdown tables: built in interval k - 1, read in k
-constexpr int kRingMirror = kTile;    // ring entries repeated past its end (ring_store)
 // Key-row pairs in flight in the 16-wave (ONE_TRIP) compare: 2, 4, 8 and 16 are within 0.5 %
 // of each other on config 5's shard (round 4); the whole 10,000-symbol workload ran 3 % slower
 // with 16 and no VGPR cap, so 2.
 constexpr int kCmpDepth1 = 2;
-
-struct SmaLds {                       // byte offsets into dynamic LDS
-    size_t ring, keys, dst, ct, ql, nar, ctr, total;
-};
-
-__host__ __device__ inline SmaLds sma_lds_layout(int ring, int nw) {
-    SmaLds L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 15) & ~size_t(15); return r; };
-    L.ring = take((size_t)(ring + kRingMirror) * 8);
-    const int nwp = (nw + kKeyGrab - 1) / kKeyGrab * kKeyGrab;  // key rows: whole groups
-    L.keys = take((size_t)2 * nwp * kKS * 4);
-    L.dst = take((size_t)kDstStages * kDstLevels * kTile * sizeof(Agg));
-    L.ct = take((size_t)kStages * kTile * 4);
-    L.ql = take((size_t)kStages * 2 * kTile * 8);
-    L.nar = take((size_t)kStages * 4);    // per tile stage: accounts fit int32 (SmaAcct)
-    L.ctr = take(4);
-    L.total = o;
-    return L;
-}
 
 // Stage 1 for one tile, executed by one whole wave (lane = bar of the tile).
 struct ScanCarry {
@@ -949,75 +927,29 @@ __global__ __launch_bounds__(256) void sma_seg_combine(const SymDesc* __restrict
     wave_add_trades(out, ntr);
 }
 
-size_t sma_lds_bytes(const Grid& g) { return sma_lds_layout(g.ring, g.na + g.nb).total; }
-
-// Block shape: one block per symbol when the parameters fit (<= 15 parameter waves + a helper,
-// or exactly 16 waves with the scan folded into the last parameter wave), otherwise the fewest
-// equal y-blocks; each y-block recomputes the tile scan and keys, so splits are avoided.
-SmaShape sma_shape(int P) {
-    const int need = (P + 63) / 64;
-    SmaShape s;
-    if (need == 16) {
-        s.pw = 16;
-        s.dedicated = 0;
-    } else {
-        const int nby = (need + 14) / 15;
-        s.pw = (need + nby - 1) / nby;
-        s.dedicated = 1;
-    }
-    s.block = 64 * (s.pw + s.dedicated);
-    s.gy = (P + 64 * s.pw - 1) / (64 * s.pw);
-    return s;
-}
-
-// Bar segments for a shard of one-block-per-CU symbols (16-wave blocks: config 5) that fills the
-// GPU only a few times over: block times vary with each symbol's trade count, so the launch ends
-// with the CU whose few blocks took longest (config 5's 1,250-symbol 8-GPU shard: 4.9 blocks per
-// CU, 121 us per symbol against 107 at 10,000 symbols). Cutting each symbol into G segments gives
-// G times as many, shorter blocks. A segment costs its burn-in tiles and a ring-only lookback
-// over the longest window (about a twentieth of a tile each): G is kept where that stays under 2 %
-// of a segment. Shapes of several blocks per CU (config 2) keep G = 1.
-int32_t sma_auto_segments(int32_t n_sym, int32_t n_params, int32_t max_bars, int32_t wmax,
-                          int32_t burn_tiles) {
-    if (n_sym <= 0) return 1;
-    const SmaShape sh = sma_shape(n_params);
-    if (sh.block <= 512) return 1;
-    // enough segment blocks for ~kSegRounds rounds of one block per CU (config 5's 1,250-symbol
-    // shard, 4.9 rounds unsplit, round 4: G = 3 / 4 / 5 / 6 / 8 -> 135.0 / 133.5-134.0 /
-    // 132.4-132.5 / 132.0 / 132.5 ms; each segment adds one 128-B record per parameter)
-    constexpr double kSegRounds = 28.0;
-    const double rounds = (double)n_sym * sh.gy / device_cus();
-    if (rounds >= kSegRounds) return 1;
-    int G = std::min(8, (int)std::ceil(kSegRounds / rounds));
-    const int ntiles = (max_bars + kTile - 1) / kTile;
-    const int lookback = (wmax - 1 + kTile - 1) / kTile;
-    while (G > 1 && burn_tiles + 0.05 * lookback > 0.02 * ntiles / G) --G;
-    return G;
-}
-
 namespace {
 
 template <bool ONE_TRIP>
 hipError_t launch_sma_variant(const SymDesc* syms, int32_t n_sym, const int32_t* close,
                               const Grid& g, const Out& out, bool parity, const SegArgs& seg,
-                              hipStream_t st, const SmaShape& sh, size_t lds) {
-    const dim3 grid(n_sym, sh.gy), block(sh.block);
-    if (seg.G > 1 && !parity) {
+                              const LaunchPlan& pl, hipStream_t st) {
+    const dim3 grid(n_sym, pl.grid_y), block(pl.block);
+    if (pl.G > 1) {
         // speculative segments, the fix pass of each boundary in order (a block returns at once
         // when every lane started in the true position), then the fold
-        const dim3 sgrid(n_sym, sh.gy, seg.G), fgrid(n_sym, sh.gy, 1);
-        for (int s = 0; s < seg.G; ++s)
-            hipLaunchKernelGGL((sma_seg_kernel<ONE_TRIP>), s == 0 ? sgrid : fgrid, block, lds, st, syms,
-                               close, g, out, sh.dedicated, seg, s);
+        const dim3 sgrid(n_sym, pl.grid_y, pl.G), fgrid(n_sym, pl.grid_y, 1);
+        for (int s = 0; s < pl.G; ++s)
+            hipLaunchKernelGGL((sma_seg_kernel<ONE_TRIP>), s == 0 ? sgrid : fgrid, block, pl.lds, st, syms,
+                               close, g, out, pl.dedicated, seg, s);
         const size_t n = (size_t)n_sym * g.n_params;
         hipLaunchKernelGGL(sma_seg_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, syms, n_sym,
-                           g.n_params, reinterpret_cast<const SmaSegRec*>(seg.rec), seg.G, g.sqrt_ann, out);
+                           g.n_params, reinterpret_cast<const SmaSegRec*>(seg.rec), pl.G, g.sqrt_ann, out);
     } else if (parity) {
-        hipLaunchKernelGGL((sma_kernel<true, false, ONE_TRIP>), grid, block, lds, st, syms, close, g, out,
-                           sh.dedicated);
+        hipLaunchKernelGGL((sma_kernel<true, false, ONE_TRIP>), grid, block, pl.lds, st, syms, close, g, out,
+                           pl.dedicated);
     } else {
-        hipLaunchKernelGGL((sma_kernel<false, false, ONE_TRIP>), grid, block, lds, st, syms, close, g, out,
-                           sh.dedicated);
+        hipLaunchKernelGGL((sma_kernel<false, false, ONE_TRIP>), grid, block, pl.lds, st, syms, close, g, out,
+                           pl.dedicated);
     }
     return hipGetLastError();
 }
@@ -1025,25 +957,18 @@ hipError_t launch_sma_variant(const SymDesc* syms, int32_t n_sym, const int32_t*
 }  // namespace
 
 hipError_t launch_sma(const SymDesc* syms, int32_t n_sym, const int32_t* close, const Grid& g,
-                      const Out& out, bool parity, const SegArgs& seg, hipStream_t st) {
+                      const Out& out, bool parity, const SegArgs& seg, const LaunchPlan& pl,
+                      hipStream_t st) {
     if (n_sym <= 0) return hipSuccess;
-    const SmaShape sh = sma_shape(g.n_params);
-    size_t lds = sma_lds_bytes(g);
-    // blocks of more than 8 waves (config 5: one 16-wave block per CU) hide little LDS latency:
-    // their reversal loop issues all of an iteration's reads before one wait
-    bool one_trip = sh.block > 512;
 #ifdef BT_PROFILING
-    if (BT_ABL(g, 128)) lds = std::max(lds, (size_t)(g.ablate & 256 ? 80 : 60) * 1024);  // occupancy probe
-    if (const char* v = getenv("BT_ONE_TRIP")) one_trip = atoi(v) != 0;  // tuning aid
     if (BT_ABL(g, 64)) {
-        const dim3 grid(n_sym, sh.gy), block(sh.block);
-        hipLaunchKernelGGL((sma_kernel<false, true, false>), grid, block, lds, st, syms, close, g, out,
-                           sh.dedicated);
+        hipLaunchKernelGGL((sma_kernel<false, true, false>), dim3(n_sym, pl.grid_y), dim3(pl.block), pl.lds, st,
+                           syms, close, g, out, pl.dedicated);
         return hipGetLastError();
     }
 #endif
-    if (one_trip) return launch_sma_variant<true>(syms, n_sym, close, g, out, parity, seg, st, sh, lds);
-    return launch_sma_variant<false>(syms, n_sym, close, g, out, parity, seg, st, sh, lds);
+    if (pl.one_trip) return launch_sma_variant<true>(syms, n_sym, close, g, out, parity, seg, pl, st);
+    return launch_sma_variant<false>(syms, n_sym, close, g, out, parity, seg, pl, st);
 }
 
 }  // namespace bt

@@ -27,6 +27,8 @@
 
 #include <type_traits>
 
+#include "lds_layout.h"
+#include "plan.h"
 #include "tile_common.h"
 
 namespace bt {
@@ -53,24 +55,6 @@ namespace {
 #endif
 constexpr int kEmaChainPrio = BT_EMA_CHAIN_PRIO, kEmaWalkPrio = BT_EMA_WALK_PRIO;
 constexpr int kBollWalkPrio = BT_BOLL_WALK_PRIO, kBollAcctPrio = BT_BOLL_ACCT_PRIO;
-constexpr int kEStride = kTile + 1;  // ema buffer row stride (doubles): conflict-free columns
-// Bollinger tile buffers: scanned (k+2), flagged (k+1), walked (k) and accounted (k-1, by the
-// accountant wave of a split walk)
-constexpr int kBollStages = 4;
-// EMA+OLS runs stages of TS tiles per barrier (ema_tile_kernel): closes, returns and narrow
-// flags of three stages in flight (scanned st+2, flagged st+1, walked st), drawdown tables, chain
-// values and condition words of two (built / chained / flagged st+1 or st+2, read a stage later)
-__host__ __device__ constexpr int ema_ct_slots(int ts) { return 3 * ts; }
-__host__ __device__ constexpr int ema_slots(int ts) { return 2 * ts; }
-// drawdown tables: 64-bar stages build them in the scan (three stages of buffers, as the closes),
-// 128-bar stages a stage later (two)
-__host__ __device__ constexpr int ema_dst_slots(int ts) { return ts == 1 ? ema_ct_slots(1) : ema_slots(ts); }
-constexpr int kEmaTS = 2;  // 128-bar stages where the LDS allows (ema_stage_tiles)
-
-// Trade records per lane and tile: an entry needs a bar after the previous exit and an exit a bar
-// after its entry, so a tile holds at most 32 entries plus the exit of a position carried in.
-constexpr int kRecCap = 33;
-
 // EMA+OLS walk accounts in int32 while the closes' total variation allows (unsplit runs)
 #ifndef BT_EMA_NARROW
 #define BT_EMA_NARROW 1
@@ -84,55 +68,8 @@ constexpr bool kEmaNarrow = BT_EMA_NARROW;
 #endif
 constexpr bool kBollWalkNarrow = BT_BOLL_WALK_NARROW;
 
-// Bollinger per-stage low/high staging (int32): lows[64], highs[64], 8 block minima of the lows
-// then 8 block maxima of the highs, per bar the minimum low / maximum high from that bar to the
-// end of its 8-bar block, and per bar the minimum low / maximum high from that bar to the end of
-// the tile (SL/TP first-passage search)
-constexpr int kLH = 6 * kTile + 16;
+// offsets into a stage's low/high staging (lds_layout.h kLH)
 constexpr int kLhBx = 2 * kTile, kLhSuf = 2 * kTile + 16, kLhTs = 4 * kTile + 16;
-
-struct TileLds {
-    size_t r1, r2, ct, ql, dst, stl, sth, ebuf, words, win, lev, levp, levf, lvb, rec, nrec, nar, ctr, total;
-};
-
-// kind 0 = EMA+OLS (na spans, nb windows, ts tiles per stage), 1 = Bollinger (na windows, nb ks,
-// nlev SL/TP levels per side: nsl + ntp)
-__host__ __device__ inline TileLds tile_lds_layout(int kind, int ring, int na, int nb, int nlev = 0,
-                                                  int ts = kEmaTS) {
-    TileLds L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 15) & ~size_t(15); return r; };
-    // tile buffers: Bollinger kBollStages (one per 64-bar pipeline stage); EMA ema_ct_slots
-    // for closes / returns / narrow flags and ema_slots for tables, chain values and words
-    const int ns = kind == 1 ? kBollStages : ema_ct_slots(ts), nd = kind == 1 ? kBollStages : ema_dst_slots(ts);
-    L.r1 = take((size_t)ring * 8);
-    L.r2 = take((size_t)ring * (kind == 0 ? 8 : 16));
-    L.ct = take((size_t)ns * kTile * 4);
-    L.ql = take((size_t)ns * 2 * kTile * 8);
-    L.dst = take((size_t)nd * kDstLevels * kTile * sizeof(Agg));
-    if (kind == 1) {
-        L.stl = take((size_t)ns * kLH * 4);  // lows, highs, block and in-block suffix extrema
-        L.ebuf = take((size_t)nb * 8);                              // k_num^2 as doubles
-        L.words = take((size_t)2 * (na * nb + 2 * na) * 8);
-        L.win = take((size_t)na * 4);
-        L.lev = take((size_t)2 * 2 * nlev * kTile);  // first-passage bars, [tile & 1][side][level][bar]
-        L.levp = take((size_t)3 * 2 * nlev * kTile * 4);  // the levels (int32), [tile % 3][side][level][bar]
-        L.levf = take((size_t)2 * nlev * 8);         // level factors per side
-        L.lvb = take((size_t)(nlev + 1) * 4);        // distinct SL/TP bps, then their count
-        // the finder's trade records [tile & 1][record][lane] and records per lane [tile & 1][lane]
-        L.rec = take((size_t)2 * kRecCap * kTile * 2);
-        L.nrec = take((size_t)2 * kTile);
-        L.nar = take((size_t)ns * 4);  // per tile stage: the accountant's sums fit int32 (Acct32)
-    } else {
-        L.ebuf = take((size_t)ema_slots(ts) * na * kEStride * 8);
-        L.words = take((size_t)ema_slots(ts) * (4 * na + 2 * nb) * 8);
-        L.win = take((size_t)nb * 4);
-        L.nar = take((size_t)ns * 4);  // per tile stage: the walk's accounts fit int32 (Acct32)
-    }
-    L.ctr = take(4);
-    L.total = o;
-    return L;
-}
 
 __device__ __forceinline__ int32_t ldc(const int32_t* __restrict__ row, int B, int t, int32_t pad) {
     return t < B ? row[t] : pad;
@@ -150,7 +87,7 @@ __device__ __forceinline__ uint32_t grab_issue(uint32_t* ctr, int lane) {
 __device__ __forceinline__ uint32_t grab_value(uint32_t v) { return __builtin_amdgcn_readlane(v, 0); }
 
 // Prefix rings: entry x (the sum over bars < x) lives at x mod R, with R a multiple of 64 of at
-// least the longest window + 3 tiles (engine.cpp), so windows up to the spec's 4,096 bars fit
+// least the longest window + 3 tiles (plan.cpp plan_grid), so windows up to the spec's 4,096 bars fit
 // in LDS. Position of x = T*64 + lane + 1, and of x - W given that position (0 < W < R).
 __device__ __forceinline__ int ring_pos(int T, int lane, int R) {
     const int p = (T % (R / kTile)) * kTile + lane + 1;
@@ -1706,221 +1643,73 @@ __global__ __launch_bounds__(256) void seg_combine(const SymDesc* __restrict__ s
 }
 
 // ----------------------------------------------------------------------------- launchers
-// Extra task-only waves per block (they take condition-word tasks only). The EMA kernel has one
-// parameter wave per symbol on config 3 and is latency-bound at ~1.5 waves per SIMD: two extra
-// waves take 4.96 -> 3.68 ms, four (with the parameter wave walking only, at raised priority)
-// 3.32 ms, five 3.20 ms (8 waves: two blocks per CU still fit); six no longer fit two blocks per
-// CU (5.0 ms). The Bollinger kernel runs 5 waves x 2 blocks per CU and its ~120 VGPRs cap a
-// CU at 16 waves: two task-only waves, with the parameter waves then walking only, take config 4
-// 12.3 -> 12.0 ms (250 symbols: 9.95 -> 9.76 ms); four no longer fit two blocks (19.4 ms).
-static int tile_param_waves(int need, int cap) {
-    int pw = std::min(need, cap);
-#ifdef BT_PROFILING
-    if (const char* v = getenv("BT_PW")) pw = std::max(1, std::min(atoi(v), pw));  // tuning aid
-#endif
-    return pw;
-}
+// The launches of one run, shared by the two tile kernels. `kernel(variant, grid, s)` enqueues the
+// strategy's kernel: a split run is the speculative segments, then the fix pass of each boundary
+// in order (a block returns at once when its lanes' starts were right), then the fold.
+enum class Variant { kPlain, kParity, kSeg };
+template <Variant V>
+using VariantTag = std::integral_constant<Variant, V>;
 
-// Hardware wave -> role of a Bollinger block (k_tile boll_tile_kernel wave_map). Hardware wave w
-// runs on SIMD w % 4, so waves w and w + 4 share one: each busy parameter wave (the walks, the
-// busiest first) gets a task-only wave as its partner (task waves take fewer tasks when their
-// SIMD is busy), the lightest parameter wave the helper, and the accountant of a split walk a
-// light parameter wave. Identity for other block shapes.
-static uint32_t boll_wave_map(int pw, int nsplit, int xw) {
-    uint32_t m = 0;
-    for (int w = 0; w < 8; ++w) m |= (uint32_t)w << (4 * w);
-    const int nw = pw + 1 + nsplit + xw;
-    if (nw == 8 && pw == 4) {
-        // logical roles: 0-3 parameter groups, 4 helper, then the accountant, then tasks
-        const int split_map[8] = {0, 1, 2, 3, 6, 7, 5, 4};
-        const int plain_map[8] = {0, 1, 2, 3, 5, 6, 7, 4};
-        const int* r = nsplit == 1 ? split_map : plain_map;
-        m = 0;
-        for (int w = 0; w < 8; ++w) m |= (uint32_t)r[w] << (4 * w);
+template <class K>
+static hipError_t launch_tile_run(const K& kernel, const SymDesc* syms, int32_t n_sym, const Grid& g,
+                                  const Out& out, bool parity, const SegArgs& seg, const LaunchPlan& pl,
+                                  hipStream_t st) {
+    const dim3 grid(n_sym, pl.grid_y, pl.G), fgrid(n_sym, pl.grid_y, 1);
+    if (pl.G > 1) {
+        kernel(VariantTag<Variant::kSeg>{}, grid, 0);
+        for (int s = 1; s < pl.G; ++s) kernel(VariantTag<Variant::kSeg>{}, fgrid, s);
+        const size_t n = (size_t)n_sym * g.n_params;
+        hipLaunchKernelGGL(seg_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, syms, n_sym, g.n_params, seg.rec, pl.G, g.sqrt_ann, out);
+    } else if (parity) {
+        kernel(VariantTag<Variant::kParity>{}, grid, 0);
+    } else {
+        kernel(VariantTag<Variant::kPlain>{}, grid, 0);
     }
-#ifdef BT_PROFILING
-    if (const char* v = getenv("BT_WAVEMAP")) m = (uint32_t)strtoul(v, nullptr, 16);  // tuning aid
-#endif
-    return m;
-}
-
-// Split Bollinger walk (finder + accountant waves) on by default; BT_SPLIT=0 turns it off in the
-// profiling build (A/B aid).
-static bool tile_split_walk() {
-    bool on = true;
-#ifdef BT_PROFILING
-    if (const char* v = getenv("BT_SPLIT")) on = atoi(v) != 0;
-#endif
-    return on;
-}
-
-static int tile_lanes_per_wave() {
-    int l = 64;
-#ifdef BT_PROFILING
-    if (const char* v = getenv("BT_LPW")) l = std::max(1, std::min(atoi(v), 64));  // tuning aid
-#endif
-    return l;
-}
-
-// Compute units of the current device (one process per GPU).
-int device_cus() {
-    static int n = 0;
-    if (n <= 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
-}
-
-static int tile_extra_waves(int used, int x) {
-#ifdef BT_PROFILING
-    if (const char* v = getenv("BT_XW")) x = atoi(v);  // tuning aid
-#endif
-    return std::max(0, std::min(x, 16 - used));
-}
-
-size_t ema_lds_bytes(const Grid& g, int ts) { return tile_lds_layout(0, g.ring, g.na, g.nb, 0, ts).total; }
-size_t boll_lds_bytes(const Grid& g) {
-    return tile_lds_layout(1, g.ring, g.na, g.nb, g.nc + g.nd).total;
-}
-
-int32_t ema_burn_tiles(int32_t max_span) {
-    // fp64 EMA chains started from e = c met the true ones after 131-162 bars (span 10) to
-    // 11,559-13,368 bars (span 780) over 18 starts each (round-2 measurement); started from the
-    // weighted-sum estimate, after at most 2.6 (span 10) to 3.8 (span 780) spans (round 3,
-    // 18 starts each): 6 spans, on top of the OLS lookback tiles the chain also runs through
-    return std::max(kDefaultBurnTiles, (6 * max_span + kTile - 1) / kTile);
-}
-
-int32_t ema_auto_segments(int32_t n_sym, int32_t n_params, int32_t max_bars, int32_t burn_tiles) {
-    if (n_sym <= 0) return 1;
-    const int pw = std::min((n_params + 63) / 64, 1024 / 64 - 2);
-    const long long blocks = (long long)n_sym * ((n_params + 64 * pw - 1) / (64 * pw));
-    if (blocks > device_cus()) return 1;
-    int G = (int)std::min<long long>(4, std::max<long long>(1, 2LL * device_cus() / blocks));
-    const int ntiles = (max_bars + kTile - 1) / kTile;
-    while (G > 1 && ntiles / G < 2 * burn_tiles) --G;
-    return G;
-}
-
-// Tiles per stage of an EMA+OLS launch: 128-bar stages (TS = 2) when they keep as many blocks per
-// CU as 64-bar ones (config 3: 80.2 KB vs 61.1 KB, two either way), else TS = 1.
-int ema_stage_tiles(const Grid& g) {
-    const size_t cu = 160 * 1024, l1 = ema_lds_bytes(g, 1), l2 = ema_lds_bytes(g, 2);
-    return l2 <= cu && cu / l2 >= cu / l1 ? 2 : 1;
+    return hipGetLastError();
 }
 
 template <int TS>
 static hipError_t launch_ema_ts(const SymDesc* syms, int32_t n_sym, const int32_t* close, const Grid& g,
-                                const Out& out, bool parity, const SegArgs& seg, hipStream_t st) {
-    const int lpw = tile_lanes_per_wave();
-    const int pw = tile_param_waves((g.n_params + lpw - 1) / lpw, 1024 / 64 - 2);
-    const int xw = tile_extra_waves(pw + 2, 5);
-    const bool split = seg.G > 1 && !parity;
-    const dim3 grid(n_sym, (g.n_params + lpw * pw - 1) / (lpw * pw), split ? seg.G : 1);
-    const dim3 block(64 * (pw + 2 + xw));
-    const size_t lds = ema_lds_bytes(g, TS);
+                                const Out& out, bool parity, const SegArgs& seg, const LaunchPlan& pl,
+                                hipStream_t st) {
+    const dim3 block(pl.block);
+    auto kernel = [&](auto v, dim3 grid, int s) {
+        constexpr bool kPar = decltype(v)::value == Variant::kParity, kSeg = decltype(v)::value == Variant::kSeg;
 #ifdef BT_PROFILING
-    if (BT_ABL(g, 64) && !split) {
-        hipLaunchKernelGGL((ema_tile_kernel<false, true, false, TS>), grid, block, lds, st, syms, close, g, out, xw, lpw, seg, 0);
-        return hipGetLastError();
-    }
+        if (BT_ABL(g, 64) && s == 0) {  // the unsplit run or the speculative segments, stamped
+            hipLaunchKernelGGL((ema_tile_kernel<false, true, kSeg, TS>), grid, block, pl.lds, st, syms, close, g, out, pl.xw, pl.lpw, seg, 0);
+            return;
+        }
 #endif
-    if (split) {
-        // speculative segments (stamped in the profiling build), the fix pass of each boundary,
-        // the fold
-#ifdef BT_PROFILING
-        if (BT_ABL(g, 64))
-            hipLaunchKernelGGL((ema_tile_kernel<false, true, true, TS>), grid, block, lds, st, syms, close, g, out, xw, lpw, seg, 0);
-        else
-#endif
-            hipLaunchKernelGGL((ema_tile_kernel<false, false, true, TS>), grid, block, lds, st, syms, close, g, out, xw, lpw, seg, 0);
-        const dim3 fgrid(grid.x, grid.y, 1);
-        for (int s = 1; s < seg.G; ++s)
-            hipLaunchKernelGGL((ema_tile_kernel<false, false, true, TS>), fgrid, block, lds, st, syms, close, g, out, xw, lpw, seg, s);
-        const size_t n = (size_t)n_sym * g.n_params;
-        hipLaunchKernelGGL(seg_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, syms, n_sym, g.n_params, seg.rec, seg.G, g.sqrt_ann, out);
-    } else if (parity) {
-        hipLaunchKernelGGL((ema_tile_kernel<true, false, false, TS>), grid, block, lds, st, syms, close, g, out, xw, lpw, seg, 0);
-    } else {
-        hipLaunchKernelGGL((ema_tile_kernel<false, false, false, TS>), grid, block, lds, st, syms, close, g, out, xw, lpw, seg, 0);
-    }
-    return hipGetLastError();
+        hipLaunchKernelGGL((ema_tile_kernel<kPar, false, kSeg, TS>), grid, block, pl.lds, st, syms, close, g, out, pl.xw, pl.lpw, seg, s);
+    };
+    return launch_tile_run(kernel, syms, n_sym, g, out, parity, seg, pl, st);
 }
 
 hipError_t launch_ema_ols(const SymDesc* syms, int32_t n_sym, const int32_t* close, const Grid& g,
-                          const Out& out, bool parity, const SegArgs& seg, hipStream_t st) {
+                          const Out& out, bool parity, const SegArgs& seg, const LaunchPlan& pl,
+                          hipStream_t st) {
     if (n_sym <= 0) return hipSuccess;
-    return ema_stage_tiles(g) == 2 ? launch_ema_ts<2>(syms, n_sym, close, g, out, parity, seg, st)
-                                   : launch_ema_ts<1>(syms, n_sym, close, g, out, parity, seg, st);
-}
-
-// Bar segments per symbol for a shard of n_sym symbols: a shard with no more blocks than CUs
-// leaves every CU one latency-bound block (config 4 on 8 GPUs: 250 symbols, 7.95 ms), so its
-// series are cut into up to 4 segments, enough for two blocks per CU, each segment at least
-// twice the burn-in long.
-int32_t boll_auto_segments(int32_t n_sym, int32_t n_params, int32_t max_bars) {
-    if (n_sym <= 0) return 1;
-    const int pw = std::min((n_params + 63) / 64, 1024 / 64 - 1);
-    const long long blocks = (long long)n_sym * ((n_params + 64 * pw - 1) / (64 * pw));
-    if (blocks > device_cus()) return 1;
-    int G = (int)std::min<long long>(4, std::max<long long>(1, 2LL * device_cus() / blocks));
-    const int ntiles = (max_bars + kTile - 1) / kTile;
-    while (G > 1 && ntiles / G < 2 * kDefaultBurnTiles) --G;
-    return G;
+    return pl.ts == 2 ? launch_ema_ts<2>(syms, n_sym, close, g, out, parity, seg, pl, st)
+                      : launch_ema_ts<1>(syms, n_sym, close, g, out, parity, seg, pl, st);
 }
 
 hipError_t launch_boll(const SymDesc* syms, int32_t n_sym, const int32_t* high, const int32_t* low,
                        const int32_t* close, const Grid& g, const Out& out, bool parity,
-                       const SegArgs& seg, hipStream_t st) {
+                       const SegArgs& seg, const LaunchPlan& pl, hipStream_t st) {
     if (n_sym <= 0) return hipSuccess;
-    const int lpw = tile_lanes_per_wave();
-    const int pw = tile_param_waves((g.n_params + lpw - 1) / lpw, 1024 / 64 - 1);
-    const bool split = seg.G > 1 && !parity;
-    const dim3 grid(n_sym, (g.n_params + lpw * pw - 1) / (lpw * pw), split ? seg.G : 1);
-    // Split walk: the parameter wave holding the smallest z threshold (lanes run k-major) trades
-    // the most, and its lanes' serial trade chains set the tile time (config 4: 7.1 walk
-    // iterations per tile against 1.0-4.3 for the other waves), so that wave only finds trades
-    // and an accountant wave keeps their accounts a tile later.
-    int split_grp = -1;
-    if (tile_split_walk() && pw >= 2 && grid.y == 1) {
-        const long long per_k = (long long)g.na * g.nc * g.nd;  // lanes per z threshold
-        const int grp = (int)((g.kmin_idx * per_k) / lpw);
-        if (grp < pw) split_grp = grp;
-    }
-    const int nsplit = split_grp < 0 ? 0 : 1;
-    const int base = pw + 1 + nsplit;
-    // at most one block per CU (config 4 on 8 GPUs: 250 symbols) leaves wave slots free: four
-    // task-only waves (8.17 -> 7.90 ms vs two); otherwise as many as keep the block at 8 waves,
-    // so two blocks share a CU at <= 128 VGPRs (config 4: three, 9.65 -> 9.51 ms; four 15.8 ms)
-    const bool sparse = (long long)grid.x * grid.y * grid.z <= device_cus();
-    const int xw = tile_extra_waves(base, sparse ? 4 : std::max(2, std::min(3, 8 - base)));
-    const dim3 block(64 * (base + xw));
-    const size_t lds = boll_lds_bytes(g);
-    const uint32_t wmap = boll_wave_map(pw, nsplit, xw);
+    const dim3 block(pl.block);
 #ifdef BT_PROFILING
     if (BT_ABL(g, 64)) {
-        hipLaunchKernelGGL((boll_tile_kernel<false, true, false>), grid, block, lds, st, syms, high, low, close, g, out, xw, lpw, seg, 0, split_grp, wmap);
+        hipLaunchKernelGGL((boll_tile_kernel<false, true, false>), dim3(n_sym, pl.grid_y, pl.G), block, pl.lds, st, syms, high, low, close, g, out, pl.xw, pl.lpw, seg, 0, pl.split_grp, pl.wmap);
         return hipGetLastError();
     }
 #endif
-    if (split) {
-        // speculative segments, then the fix pass of each boundary in order (a block returns at
-        // once when its lanes' starts were right), then the fold
-        hipLaunchKernelGGL((boll_tile_kernel<false, false, true>), grid, block, lds, st, syms, high, low, close, g, out, xw, lpw, seg, 0, split_grp, wmap);
-        const dim3 fgrid(grid.x, grid.y, 1);
-        for (int s = 1; s < seg.G; ++s)
-            hipLaunchKernelGGL((boll_tile_kernel<false, false, true>), fgrid, block, lds, st, syms, high, low, close, g, out, xw, lpw, seg, s, split_grp, wmap);
-        const size_t n = (size_t)n_sym * g.n_params;
-        hipLaunchKernelGGL(seg_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, syms, n_sym, g.n_params, seg.rec, seg.G, g.sqrt_ann, out);
-    } else if (parity) {
-        hipLaunchKernelGGL((boll_tile_kernel<true, false, false>), grid, block, lds, st, syms, high, low, close, g, out, xw, lpw, seg, 0, split_grp, wmap);
-    } else {
-        hipLaunchKernelGGL((boll_tile_kernel<false, false, false>), grid, block, lds, st, syms, high, low, close, g, out, xw, lpw, seg, 0, split_grp, wmap);
-    }
-    return hipGetLastError();
+    auto kernel = [&](auto v, dim3 grid, int s) {
+        constexpr bool kPar = decltype(v)::value == Variant::kParity, kSeg = decltype(v)::value == Variant::kSeg;
+        hipLaunchKernelGGL((boll_tile_kernel<kPar, false, kSeg>), grid, block, pl.lds, st, syms, high, low, close, g, out, pl.xw, pl.lpw, seg, s, pl.split_grp, pl.wmap);
+    };
+    return launch_tile_run(kernel, syms, n_sym, g, out, parity, seg, pl, st);
 }
 
 }  // namespace bt

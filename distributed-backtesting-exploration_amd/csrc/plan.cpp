@@ -1,0 +1,362 @@
+// plan.cpp — the host's launch decisions (plan.h): grid validation and ring sizing, block shapes,
+// bar segments, dynamic LDS and segment buffer sizes. Pure functions: no HIP call, no device
+// state; the profiling build's environment overrides sit next to the rules they override.
+#include "plan.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+
+#include "csv.h"
+#include "lds_layout.h"
+
+namespace bt {
+
+namespace {
+
+constexpr int kDefaultBurnTiles = 64;  // tile kernels
+constexpr int kSmaBurnTiles = 2;
+
+uint32_t next_pow2(uint32_t x) {
+    uint32_t r = 1;
+    while (r < x) r <<= 1;
+    return r;
+}
+
+size_t ema_lds_bytes(const Grid& g, int ts) { return tile_lds_layout(0, g.ring, g.na, g.nb, 0, ts).total; }
+
+}  // namespace
+
+// ------------------------------------------------------------------------ grid configuration
+int config_axes(const bt_config& c, AxisSpec ax[4]) {
+    switch (c.strategy) {
+        case BT_SMA_CROSS:
+            ax[0] = {c.fast, c.n_fast, "fast", 1, kMaxBars};
+            ax[1] = {c.slow, c.n_slow, "slow", 1, kMaxBars};
+            return 2;
+        case BT_EMA_OLS:
+            ax[0] = {c.span, c.n_span, "span", 1, kMaxBars};
+            ax[1] = {c.ols, c.n_ols, "ols", 1, 1 << 16};
+            return 2;
+        case BT_BOLL:
+            ax[0] = {c.bwin, c.n_bwin, "bwin", 1, 1 << 16};
+            ax[1] = {c.k_num, c.n_k, "k_num", 0, 1 << 20};
+            ax[2] = {c.sl_bps, c.n_sl, "sl_bps", 0, 9999};
+            ax[3] = {c.tp_bps, c.n_tp, "tp_bps", 0, 9999};
+            return 4;
+        default:
+            return 0;
+    }
+}
+
+std::string plan_grid(const bt_config& c, Grid& g) {
+    AxisSpec ax[4];
+    const int nax = config_axes(c, ax);
+    if (nax == 0) return "unknown strategy";
+    for (int i = 0; i < nax; ++i) {
+        if (ax[i].n <= 0 || ax[i].v == nullptr) return std::string("empty axis: ") + ax[i].what;
+        for (int32_t j = 0; j < ax[i].n; ++j)
+            if (ax[i].v[j] < ax[i].lo || ax[i].v[j] > ax[i].hi)
+                return std::string("value out of range on axis ") + ax[i].what + ": " + std::to_string(ax[i].v[j]);
+    }
+    auto amax = [&](int i) { return *std::max_element(ax[i].v, ax[i].v + ax[i].n); };
+    g.strategy = c.strategy;
+    g.na = ax[0].n;
+    g.nb = ax[1].n;
+    g.nc = nax > 2 ? ax[2].n : 1;
+    g.nd = nax > 3 ? ax[3].n : 1;
+    switch (c.strategy) {
+        case BT_SMA_CROSS:
+            g.wmax = std::max(amax(0), amax(1));
+            // prefix ring, a power of two: the longest window back from the tile whose keys are
+            // built, with three tiles in flight (k_sma.hip: scan k+2, keys k+1, compare k)
+            g.ring = (int32_t)next_pow2((uint32_t)g.wmax + 3 * kTile);
+            if (sma_lds_layout(g.ring, g.na + g.nb).total > kCuLdsBytes)
+                return "SMA grid needs more LDS than a CU has (windows too long)";
+            break;
+        case BT_EMA_OLS:
+            if (c.band_bps < 0 || c.band_bps >= 10000) return "band_bps out of range";
+            if (c.n_span > 64) return "EMA grid: at most 64 spans (one helper lane per span)";
+            g.band_bps = c.band_bps;
+            g.wmax = amax(1);
+            // prefix ring, rounded up to a multiple of the tile: a window back from the stage being
+            // flagged, which ends two 128-bar stages (four tiles) before the last scanned bar
+            // (k_tile.hip ema_tile_kernel)
+            g.ring = (g.wmax + 5 * kTile - 1) / kTile * kTile;
+            if (ema_lds_bytes(g, 1) > kCuLdsBytes) return "EMA grid needs more LDS than a CU has (OLS windows too long)";
+            break;
+        default: {
+            if (c.k_den < 1 || c.k_den > (1 << 20)) return "k_den out of range";
+            g.k_den = c.k_den;
+            g.wmax = amax(0);
+            // z tests D^2 kd^2 vs kn^2 Q with D^2, Q < w^2 2^62: exact in int128 while
+            // w * max(k_num, k_den) < 2^32 (spec §4, oracle/oracle.c orc_boll)
+            const int64_t kmax = std::max<int64_t>(c.k_den, amax(1));
+            if ((int64_t)g.wmax * kmax >= (1LL << 32)) return "Bollinger grid outside the exact int128 range (window * k >= 2^32)";
+            // prefix rings: the longest window + three tiles in flight (k_tile.hip: scanned k+2,
+            // flagged k+1, walked k), rounded up to a multiple of the tile
+            g.ring = (g.wmax + 4 * kTile - 1) / kTile * kTile;
+            for (int q = 0; q < 8; ++q) {
+                const int64_t kn = q < c.n_k ? c.k_num[q] : 0;
+                g.kn2[q] = (double)(kn * kn);  // exact: kn <= 2^20
+            }
+            g.kmin_idx = (int32_t)(std::min_element(c.k_num, c.k_num + c.n_k) - c.k_num);
+            if (tile_lds_layout(1, g.ring, g.na, g.nb, g.nc + g.nd).total > kCuLdsBytes)
+                return "Bollinger grid needs more LDS than a CU has (windows too long)";
+            break;
+        }
+    }
+    const int64_t P = (int64_t)g.na * g.nb * g.nc * g.nd;
+    if (P <= 0 || P > (1 << 20)) return "parameter grid too large";
+    g.n_params = (int32_t)P;
+    return "";
+}
+
+// -------------------------------------------------------------------------------- launch plans
+namespace {
+
+// Segment records of a split run: one per (segment, symbol, param).
+size_t seg_records(const LaunchPlan& pl, const Grid& g, const RunShape& r) {
+    return pl.G > 1 ? (size_t)pl.G * r.n_sym * g.n_params : 0;
+}
+
+struct SmaShape {
+    int pw;                           // parameter waves per block
+    int dedicated;                    // 1: an extra helper wave runs the tile scan
+    int block, gy;                    // threads per block, y-blocks per symbol
+};
+
+// Block shape: one block per symbol when the parameters fit (<= 15 parameter waves + a helper,
+// or exactly 16 waves with the scan folded into the last parameter wave), otherwise the fewest
+// equal y-blocks; each y-block recomputes the tile scan and keys, so splits are avoided.
+SmaShape sma_shape(int P) {
+    const int need = (P + 63) / 64;
+    SmaShape s;
+    if (need == 16) {
+        s.pw = 16;
+        s.dedicated = 0;
+    } else {
+        const int nby = (need + 14) / 15;
+        s.pw = (need + nby - 1) / nby;
+        s.dedicated = 1;
+    }
+    s.block = 64 * (s.pw + s.dedicated);
+    s.gy = (P + 64 * s.pw - 1) / (64 * s.pw);
+    return s;
+}
+
+// Bar segments for a shard of one-block-per-CU symbols (16-wave blocks: config 5) that fills the
+// GPU only a few times over: block times vary with each symbol's trade count, so the launch ends
+// with the CU whose few blocks took longest (config 5's 1,250-symbol 8-GPU shard: 4.9 blocks per
+// CU, 121 us per symbol against 107 at 10,000 symbols). Cutting each symbol into G segments gives
+// G times as many, shorter blocks. A segment costs its burn-in tiles and a ring-only lookback
+// over the longest window (about a twentieth of a tile each): G is kept where that stays under 2 %
+// of a segment. Shapes of several blocks per CU (config 2) keep G = 1.
+int32_t sma_auto_segments(int32_t n_sym, const SmaShape& sh, int32_t max_bars, int32_t wmax,
+                          int32_t burn_tiles, int cus) {
+    if (n_sym <= 0) return 1;
+    if (sh.block <= 512) return 1;
+    // enough segment blocks for ~kSegRounds rounds of one block per CU (config 5's 1,250-symbol
+    // shard, 4.9 rounds unsplit, round 4: G = 3 / 4 / 5 / 6 / 8 -> 135.0 / 133.5-134.0 /
+    // 132.4-132.5 / 132.0 / 132.5 ms; each segment adds one 128-B record per parameter)
+    constexpr double kSegRounds = 28.0;
+    const double rounds = (double)n_sym * sh.gy / cus;
+    if (rounds >= kSegRounds) return 1;
+    int G = std::min(8, (int)std::ceil(kSegRounds / rounds));
+    const int ntiles = (max_bars + kTile - 1) / kTile;
+    const int lookback = (wmax - 1 + kTile - 1) / kTile;
+    while (G > 1 && burn_tiles + 0.05 * lookback > 0.02 * ntiles / G) --G;
+    return G;
+}
+
+void plan_sma(const Grid& g, const RunShape& r, LaunchPlan& pl) {
+    const SmaShape sh = sma_shape(g.n_params);
+    pl.burn_tiles = r.burn_req > 0 ? r.burn_req : kSmaBurnTiles;
+    if (!r.parity)
+        pl.G = r.seg_req > 0 ? r.seg_req
+                             : sma_auto_segments(r.n_sym, sh, r.max_bars, g.wmax, pl.burn_tiles, r.cus);
+    pl.grid_y = sh.gy;
+    pl.block = sh.block;
+    pl.dedicated = sh.dedicated;
+    pl.lds = sma_lds_layout(g.ring, g.na + g.nb).total;
+    // blocks of more than 8 waves (config 5: one 16-wave block per CU) hide little LDS latency:
+    // their reversal loop issues all of an iteration's reads before one wait
+    pl.one_trip = sh.block > 512;
+#ifdef BT_PROFILING
+    if (BT_ABL(g, 128)) pl.lds = std::max(pl.lds, (size_t)(g.ablate & 256 ? 80 : 60) * 1024);  // occupancy probe
+    if (const char* v = getenv("BT_ONE_TRIP")) pl.one_trip = atoi(v) != 0;  // tuning aid
+#endif
+    // one SegRec slot per SmaSegRec, then the int8 start / end position planes
+    const size_t nrec = seg_records(pl, g, r);
+    pl.pos_off = nrec * sizeof(SegRec);
+    pl.pos_bytes = 2 * nrec;
+    pl.seg_slots = nrec + (pl.pos_bytes + sizeof(SegRec) - 1) / sizeof(SegRec);
+}
+
+// ------------------------------------------------------------------------- tile kernel plans
+// Extra task-only waves per block (they take condition-word tasks only). The EMA kernel has one
+// parameter wave per symbol on config 3 and is latency-bound at ~1.5 waves per SIMD: two extra
+// waves take 4.96 -> 3.68 ms, four (with the parameter wave walking only, at raised priority)
+// 3.32 ms, five 3.20 ms (8 waves: two blocks per CU still fit); six no longer fit two blocks per
+// CU (5.0 ms). The Bollinger kernel runs 5 waves x 2 blocks per CU and its ~120 VGPRs cap a
+// CU at 16 waves: two task-only waves, with the parameter waves then walking only, take config 4
+// 12.3 -> 12.0 ms (250 symbols: 9.95 -> 9.76 ms); four no longer fit two blocks (19.4 ms).
+int tile_param_waves(int need, int cap) {
+    int pw = std::min(need, cap);
+#ifdef BT_PROFILING
+    if (const char* v = getenv("BT_PW")) pw = std::max(1, std::min(atoi(v), pw));  // tuning aid
+#endif
+    return pw;
+}
+
+int tile_extra_waves(int used, int x) {
+#ifdef BT_PROFILING
+    if (const char* v = getenv("BT_XW")) x = atoi(v);  // tuning aid
+#endif
+    return std::max(0, std::min(x, 16 - used));
+}
+
+int tile_lanes_per_wave() {
+    int l = 64;
+#ifdef BT_PROFILING
+    if (const char* v = getenv("BT_LPW")) l = std::max(1, std::min(atoi(v), 64));  // tuning aid
+#endif
+    return l;
+}
+
+// Hardware wave -> role of a Bollinger block (k_tile boll_tile_kernel wave_map). Hardware wave w
+// runs on SIMD w % 4, so waves w and w + 4 share one: each busy parameter wave (the walks, the
+// busiest first) gets a task-only wave as its partner (task waves take fewer tasks when their
+// SIMD is busy), the lightest parameter wave the helper, and the accountant of a split walk a
+// light parameter wave. Identity for other block shapes.
+uint32_t boll_wave_map(int pw, int nsplit, int xw) {
+    uint32_t m = 0;
+    for (int w = 0; w < 8; ++w) m |= (uint32_t)w << (4 * w);
+    const int nw = pw + 1 + nsplit + xw;
+    if (nw == 8 && pw == 4) {
+        // logical roles: 0-3 parameter groups, 4 helper, then the accountant, then tasks
+        const int split_map[8] = {0, 1, 2, 3, 6, 7, 5, 4};
+        const int plain_map[8] = {0, 1, 2, 3, 5, 6, 7, 4};
+        const int* r = nsplit == 1 ? split_map : plain_map;
+        m = 0;
+        for (int w = 0; w < 8; ++w) m |= (uint32_t)r[w] << (4 * w);
+    }
+#ifdef BT_PROFILING
+    if (const char* v = getenv("BT_WAVEMAP")) m = (uint32_t)strtoul(v, nullptr, 16);  // tuning aid
+#endif
+    return m;
+}
+
+// Split Bollinger walk (finder + accountant waves) on by default; BT_SPLIT=0 turns it off in the
+// profiling build (A/B aid).
+bool tile_split_walk() {
+    bool on = true;
+#ifdef BT_PROFILING
+    if (const char* v = getenv("BT_SPLIT")) on = atoi(v) != 0;
+#endif
+    return on;
+}
+
+// Bar segments per symbol for a shard of n_sym symbols of a tile kernel whose blocks hold
+// `helpers` waves beside the parameter waves: a shard with no more blocks than CUs leaves every
+// CU one latency-bound block (config 4 on 8 GPUs: 250 symbols, 7.95 ms), so its series are cut
+// into up to 4 segments, enough for two blocks per CU, each segment at least twice the burn-in
+// long.
+int32_t tile_auto_segments(int32_t n_sym, int32_t n_params, int32_t max_bars, int helpers,
+                           int32_t burn_tiles, int cus) {
+    if (n_sym <= 0) return 1;
+    const int pw = std::min((n_params + 63) / 64, 1024 / 64 - helpers);
+    const long long blocks = (long long)n_sym * ((n_params + 64 * pw - 1) / (64 * pw));
+    if (blocks > cus) return 1;
+    int G = (int)std::min<long long>(4, std::max<long long>(1, 2LL * cus / blocks));
+    const int ntiles = (max_bars + kTile - 1) / kTile;
+    while (G > 1 && ntiles / G < 2 * burn_tiles) --G;
+    return G;
+}
+
+// The burn-in an EMA+OLS speculative segment needs for every span's fp64 chain to meet the true
+// one bit for bit.
+int32_t ema_burn_tiles(int32_t max_span) {
+    // fp64 EMA chains started from e = c met the true ones after 131-162 bars (span 10) to
+    // 11,559-13,368 bars (span 780) over 18 starts each (round-2 measurement); started from the
+    // weighted-sum estimate, after at most 2.6 (span 10) to 3.8 (span 780) spans (round 3,
+    // 18 starts each): 6 spans, on top of the OLS lookback tiles the chain also runs through
+    return std::max(kDefaultBurnTiles, (6 * max_span + kTile - 1) / kTile);
+}
+
+// Tiles per stage of an EMA+OLS launch: 128-bar stages (TS = 2) when they keep as many blocks per
+// CU as 64-bar ones (config 3: 80.2 KB vs 61.1 KB, two either way), else TS = 1.
+int ema_stage_tiles(const Grid& g) {
+    const size_t cu = kCuLdsBytes, l1 = ema_lds_bytes(g, 1), l2 = ema_lds_bytes(g, 2);
+    return l2 <= cu && cu / l2 >= cu / l1 ? 2 : 1;
+}
+
+void plan_ema(const Grid& g, const int32_t* spans, const RunShape& r, LaunchPlan& pl) {
+    int32_t maxspan = 1;
+    for (int32_t i = 0; i < g.na; ++i) maxspan = std::max(maxspan, spans[i]);
+    // the default burn-in lets every span's chain meet the true one; an explicit one
+    // (bt_set_segments) is honoured, the fix pass covering a short one
+    pl.burn_tiles = r.burn_req > 0 ? r.burn_req : ema_burn_tiles(maxspan);
+    if (!r.parity)
+        pl.G = r.seg_req > 0 ? r.seg_req
+                             : tile_auto_segments(r.n_sym, g.n_params, r.max_bars, 2, pl.burn_tiles, r.cus);
+    pl.lpw = tile_lanes_per_wave();
+    const int pw = tile_param_waves((g.n_params + pl.lpw - 1) / pl.lpw, 1024 / 64 - 2);
+    pl.xw = tile_extra_waves(pw + 2, 5);
+    pl.grid_y = (g.n_params + pl.lpw * pw - 1) / (pl.lpw * pw);
+    pl.block = 64 * (pw + 2 + pl.xw);
+    pl.ts = ema_stage_tiles(g);
+    pl.lds = ema_lds_bytes(g, pl.ts);
+    pl.seg_slots = seg_records(pl, g, r);
+    pl.ema_doubles = pl.G > 1 ? (size_t)pl.G * r.n_sym * kEmaSegStride : 0;
+    // the chain's histograms take no LDS beside a strategy kernel whose blocks fill a CU's
+    // (128-bar stages: k_topk.hip topk_hist_global)
+    pl.topk_lds_free = pl.ts == 2;
+}
+
+void plan_boll(const Grid& g, const RunShape& r, LaunchPlan& pl) {
+    pl.burn_tiles = r.burn_req > 0 ? r.burn_req : kDefaultBurnTiles;
+    // the automatic count assumes the default burn-in, whatever was requested
+    if (!r.parity)
+        pl.G = r.seg_req > 0 ? r.seg_req
+                             : tile_auto_segments(r.n_sym, g.n_params, r.max_bars, 1, kDefaultBurnTiles, r.cus);
+    pl.lpw = tile_lanes_per_wave();
+    const int pw = tile_param_waves((g.n_params + pl.lpw - 1) / pl.lpw, 1024 / 64 - 1);
+    pl.grid_y = (g.n_params + pl.lpw * pw - 1) / (pl.lpw * pw);
+    // Split walk: the parameter wave holding the smallest z threshold (lanes run k-major) trades
+    // the most, and its lanes' serial trade chains set the tile time (config 4: 7.1 walk
+    // iterations per tile against 1.0-4.3 for the other waves), so that wave only finds trades
+    // and an accountant wave keeps their accounts a tile later.
+    if (tile_split_walk() && pw >= 2 && pl.grid_y == 1) {
+        const long long per_k = (long long)g.na * g.nc * g.nd;  // lanes per z threshold
+        const int grp = (int)((g.kmin_idx * per_k) / pl.lpw);
+        if (grp < pw) pl.split_grp = grp;
+    }
+    const int nsplit = pl.split_grp < 0 ? 0 : 1;
+    const int base = pw + 1 + nsplit;
+    // at most one block per CU (config 4 on 8 GPUs: 250 symbols) leaves wave slots free: four
+    // task-only waves (8.17 -> 7.90 ms vs two); otherwise as many as keep the block at 8 waves,
+    // so two blocks share a CU at <= 128 VGPRs (config 4: three, 9.65 -> 9.51 ms; four 15.8 ms)
+    const bool sparse = (long long)r.n_sym * pl.grid_y * pl.G <= r.cus;
+    pl.xw = tile_extra_waves(base, sparse ? 4 : std::max(2, std::min(3, 8 - base)));
+    pl.block = 64 * (base + pl.xw);
+    pl.lds = tile_lds_layout(1, g.ring, g.na, g.nb, g.nc + g.nd).total;
+    pl.wmap = boll_wave_map(pw, nsplit, pl.xw);
+    pl.seg_slots = seg_records(pl, g, r);
+}
+
+}  // namespace
+
+LaunchPlan plan_launch(const Grid& g, const int32_t* ax0, const RunShape& r) {
+    LaunchPlan pl{};
+    pl.G = 1;
+    pl.split_grp = -1;
+    switch (g.strategy) {
+        case BT_SMA_CROSS: plan_sma(g, r, pl); break;
+        case BT_EMA_OLS: plan_ema(g, ax0, r, pl); break;
+        default: plan_boll(g, r, pl); break;
+    }
+    return pl;
+}
+
+}  // namespace bt

@@ -1,0 +1,57 @@
+// plan.h — everything the host decides before a launch, as pure functions of the configuration,
+// the dataset shape and a CU count (plan.cpp). No HIP call, no device state: the engine
+// (engine.cpp) asks for a plan and sizes its buffers from it, the launchers (k_sma.hip,
+// k_tile.hip) enqueue what it says, and tests/plan/plan_driver.cpp prints it without a GPU.
+#pragma once
+#include "internal.h"
+
+namespace bt {
+
+constexpr int kCusFallback = 256;  // CU count assumed when the device attribute cannot be read
+constexpr size_t kCuLdsBytes = 160 * 1024;
+
+// The axes of a configuration in Grid order (a, b, c, d), each with its name and the range its
+// values must lie in. Returns how many the strategy has (0: unknown strategy).
+struct AxisSpec {
+    const int32_t* v;
+    int32_t n;
+    const char* what;
+    int32_t lo, hi;
+};
+int config_axes(const bt_config& c, AxisSpec ax[4]);
+
+// Validates the parameter grid of a configuration and fills the host-side fields of `g`: strategy,
+// axis sizes, n_params, band_bps / k_den, wmax, ring, kn2 and kmin_idx (not the device pointers,
+// sqrt_ann or ablate). Returns "" or the reason the grid is refused.
+std::string plan_grid(const bt_config& c, Grid& g);
+
+// What one run is launched with.
+struct LaunchPlan {
+    int32_t G;                     // bar segments per symbol (1 = no split)
+    int32_t burn_tiles;            // tiles walked before a speculative segment's first bar
+    int32_t grid_y;                // y-blocks per symbol
+    int32_t block;                 // threads per block
+    size_t lds;                    // dynamic LDS bytes per block
+    int32_t dedicated, one_trip;   // SMA: helper wave runs the tile scan; 16-wave compare loop
+    int32_t ts;                    // EMA+OLS: tiles per stage
+    int32_t xw, lpw;               // tile kernels: task-only waves, lanes per parameter wave
+    int32_t split_grp;             // Bollinger: parameter wave whose walk is split (-1: none)
+    uint32_t wmap;                 // Bollinger: hardware wave -> role, 4 bits each
+    // segment buffers of a split run (all 0 when G == 1)
+    size_t seg_slots;              // SegRec slots of SegArgs::rec, SMA position planes included
+    size_t pos_off, pos_bytes;     // SMA: SegArgs::pos, in bytes from SegArgs::rec, and its size
+    size_t ema_doubles;            // EMA+OLS: doubles of SegArgs::ema
+    bool topk_lds_free;            // the top-k chain's histograms must take no LDS
+};
+
+struct RunShape {
+    int32_t n_sym, max_bars;       // symbols of the dataset and the longest one's bars
+    bool parity;
+    int32_t seg_req, burn_req;     // bt_set_segments: 0 = automatic / default
+    int cus;                       // compute units of the device
+};
+
+// `ax0`: the host copy of the grid's first axis (Grid::a; the EMA burn-in follows its spans).
+LaunchPlan plan_launch(const Grid& g, const int32_t* ax0, const RunShape& r);
+
+}  // namespace bt

@@ -2,7 +2,7 @@
 rule 24: compare arms on one device, in one process, alternating). Every build gets its own
 engine on the same synthetic shard; rounds alternate A, B, ... and each round times `steps`
 back-to-back runs with the engine's HIP events (bt_kernel_timing: the dominant kernel).
-The builds' summaries are compared bit for bit after the first round.
+The builds' summaries and segment counts (bt_last_segments) are compared after the first round.
 
 usage: python scripts/ab_inproc.py CONFIG SYMBOLS LIB [LIB ...]
        (LIB: in-tree path under the package, e.g. libbt.so dev/e2.so; env ROUNDS, STEPS)"""
@@ -35,13 +35,15 @@ for name in libs:
     L.bt_kernel_timing.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]
     L.bt_read_summaries.argtypes = [P, P, C.c_size_t]
     L.bt_num_params.argtypes = [P]
+    L.bt_last_segments.argtypes = [P, C.POINTER(C.c_int64)]
     conf = grid.to_c(0, 0, D.BT_FLAG_TIMING, 0, 0, None)
     err = C.create_string_buffer(512)
     h = L.bt_engine_create(C.byref(conf), err, 512)
     assert h, err.value
     assert L.bt_load_synthetic(h, 0x5EED, 0, S, bars, freq) >= 0
     arms.append((name, L, h, []))
-ref = None
+ref = ref_seg = None
+segs = {}
 for r in range(rounds):
     for name, L, h, ts in arms:
         L.bt_run(h)
@@ -56,11 +58,15 @@ for r in range(rounds):
         if r == 0:
             out = np.zeros(S * grid.n_params, D.SUMMARY_DTYPE)
             assert L.bt_read_summaries(h, out.ctypes.data, out.size) >= 0
+            segs[name] = L.bt_last_segments(h, None)
             if ref is None:
-                ref = out
-            elif out.tobytes() != ref.tobytes():
-                print(f"{name}: SUMMARIES DIFFER from {arms[0][0]}")
+                ref, ref_seg = out, segs[name]
+            else:
+                same = out.tobytes() == ref.tobytes()
+                print(f"{name}: summaries {'bit-identical to' if same else 'DIFFER from'} {arms[0][0]}")
+                if segs[name] != ref_seg:
+                    print(f"{name}: SEGMENTS DIFFER from {arms[0][0]}: {segs[name]} vs {ref_seg}")
 for name, L, h, ts in arms:
-    print(f"config {cfg} S {S} {name:16s} kernel ms median {np.median(ts):.4f} min {min(ts):.4f} "
+    print(f"config {cfg} S {S} {name:16s} segments {segs[name]} kernel ms median {np.median(ts):.4f} min {min(ts):.4f} "
           f"all {[round(x, 4) for x in ts]}")
     L.bt_engine_destroy(h)

@@ -1,7 +1,18 @@
 """Shared test helpers: oracle-vs-engine comparison (tests only)."""
+import atexit
+import functools
+import json
+import os
+import shutil
+import subprocess
+import tempfile
+
 import numpy as np
 
+import dbx_amd as D
 import orc_ffi as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def oracle_row(strategy, grid, ohlc, ann, cap=0):
@@ -57,20 +68,40 @@ def compare_trades(gpu_tr, orc_tr, n, where=""):
     assert got == exp, f"{where}: trade lists differ (first diff at {next((i for i,(a,b) in enumerate(zip(got,exp)) if a!=b), None)})"
 
 
-def ema_stage_tiles(spans, windows):
-    """Model of k_tile.hip ema_stage_tiles / tile_lds_layout(kind 0): the EMA+OLS block's LDS bytes
-    at 64-bar (TS 1) and 128-bar (TS 2) stages and the stage the launcher picks (TS 2 when it keeps
-    as many blocks per CU). Used only to choose test grids that reach each shape; pinned to the
-    kernel's own figures for config 3 (61,120 / 80,208 B) in test_tile_edge_trades.py."""
-    T, cu = 64, 160 * 1024
-    ring = (max(windows) + 5 * T - 1) // T * T
-    na, nb = len(spans), len(windows)
+@functools.lru_cache(None)
+def _plan_driver():
+    """tests/plan/plan_driver.cpp and csrc/plan.cpp built once per session, the way the Makefile
+    compiles host files (host pass only: the planner makes no HIP call and needs no GPU)."""
+    csrc = os.path.join(ROOT, "distributed-backtesting-exploration_amd", "csrc")
+    exe = os.path.join(tempfile.mkdtemp(prefix="bt_plan_"), "plan_driver")
+    atexit.register(shutil.rmtree, os.path.dirname(exe), True)
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror",
+                        "-x", "hip", "--cuda-host-only", "-I", csrc, "-I", os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests", "plan", "plan_driver.cpp"),
+                        os.path.join(csrc, "plan.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe
 
-    def lds(ts):
-        ns, nd, sl = 3 * ts, 3 if ts == 1 else 2 * ts, 2 * ts
-        parts = [ring * 8, ring * 8, ns * T * 4, ns * 2 * T * 8, nd * 6 * T * 16,
-                 sl * na * (T + 1) * 8, sl * (4 * na + 2 * nb) * 8, nb * 4, ns * 4, 4]
-        return sum((p + 15) & ~15 for p in parts)
 
-    l1, l2 = lds(1), lds(2)
-    return (2 if l2 <= cu and cu // l2 >= cu // l1 else 1), l1, l2
+@functools.lru_cache(None)
+def _plan(args):
+    out = subprocess.run([_plan_driver(), *args], capture_output=True, text=True, check=True).stdout
+    return json.loads(out)
+
+
+def launch_plan(grid, n_sym=1, bars=64, cus=256, parity=False, seg=0, burn=0):
+    """What the library launches for `grid` on a shard of n_sym symbols of at most `bars` bars on a
+    device of `cus` compute units: the real planner (csrc/plan.cpp, through tests/plan/plan_driver),
+    as a dict of the grid's ring and the LaunchPlan fields. "ema_lds" holds an EMA+OLS block's LDS
+    bytes at 64-bar and at 128-bar stages, "ts" the stage the launcher picks."""
+    name = {D.BT_SMA_CROSS: "sma", D.BT_EMA_OLS: "ema_ols", D.BT_BOLL: "boll"}[grid.strategy]
+    args = [name] + [f"{k}={','.join(str(int(v)) for v in a)}" for k, a in zip("abcd", grid.axes)]
+    args += [f"band_bps={grid.band_bps}", f"k_den={grid.k_den}", f"sym={n_sym}", f"bars={bars}",
+             f"cus={cus}", f"parity={int(parity)}", f"seg={seg}", f"burn={burn}"]
+    return dict(_plan(tuple(args)))
+
+
+def gpu_cus():
+    """Compute units of GPU 0 (GPU tests: the CU count the engine plans with)."""
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count

@@ -28,7 +28,7 @@ import pytest
 import dbx_amd as D
 import oracle_np as N
 import orc_ffi as F
-from helpers import compare_summary, compare_trades, ema_stage_tiles, oracle_row
+from helpers import compare_summary, compare_trades, launch_plan, oracle_row
 
 PMAX = 2**31 - 1
 NP_FIELDS = (("n_trades", "n"), ("pnl", "pnl"), ("mdd", "mdd"), ("exposure", "exposure"), ("hash", "h"))
@@ -191,8 +191,8 @@ def test_a_oracles_agree(name):
 
 
 def test_a_128_bar_stage_grid():
-    assert ema_stage_tiles(*A_CASES["ema_ols_128"][1]().axes[:2])[0] == 2
-    assert ema_stage_tiles(*A_CASES["ema_ols"][1]().axes[:2])[0] == 1
+    assert launch_plan(A_CASES["ema_ols_128"][1]())["ts"] == 2
+    assert launch_plan(A_CASES["ema_ols"][1]())["ts"] == 1
 
 
 @pytest.mark.gpu

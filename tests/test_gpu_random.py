@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import dbx_amd as D
-from helpers import compare_summary, compare_trades, ema_stage_tiles, oracle_row
+from helpers import compare_summary, compare_trades, launch_plan, oracle_row
 
 pytestmark = pytest.mark.gpu
 
@@ -123,13 +123,13 @@ def test_random_product_kernels(strategy, seed):
 
 
 def _ema_grid_128(rng):
-    """A random EMA+OLS grid that the launcher runs in 128-bar stages (helpers.ema_stage_tiles):
+    """A random EMA+OLS grid that the launcher runs in 128-bar stages (helpers.launch_plan):
     short random spans and windows plus one OLS window long enough (1,300-2,600 bars) that
     64-bar stages would not fit more blocks per CU."""
     for _ in range(64):
         spans = _windows(rng, int(rng.integers(2, 9)), 800)
         wins = sorted(set(_windows(rng, 3, 400) + [int(rng.integers(1300, 2600))]))
-        if ema_stage_tiles(spans, wins)[0] == 2:
+        if launch_plan(D.Grid.ema_ols(spans, wins))["ts"] == 2:
             return D.Grid.ema_ols(spans, wins, band_bps=int(rng.integers(0, 60)))
     raise AssertionError("no 128-bar-stage grid drawn")
 

@@ -7,7 +7,7 @@ import pytest
 
 import dbx_amd as D
 import orc_ffi as F
-from helpers import compare_summary, ema_stage_tiles, oracle_row
+from helpers import compare_summary, gpu_cus, launch_plan, oracle_row
 
 pytestmark = pytest.mark.gpu
 
@@ -72,10 +72,11 @@ def test_split_ragged_and_empty_segments():
 
 def test_auto_split_on_small_shard_matches_oracle():
     """Automatic mode on a shard with fewer symbols than CUs (the 8-GPU config-4 shard is 250):
-    the engine splits, and sampled symbols match the oracle."""
+    the engine splits as the planner says for this device (the 256-CU table is pinned in
+    test_launch_plan_cpu.py), and sampled symbols match the oracle."""
     grid = D.config4_grid()
     got, used, _ = _run(grid, 100, 120, 40000, 0)
-    assert used >= 2
+    assert used >= 2 and used == launch_plan(grid, 120, 40000, cus=gpu_cus())["G"]
     for s in (0, 77, 119):
         o, h, lo, c = F.gen(0x5EED, 100 + s, 40000, 1)[:4]
         orc, _ = oracle_row("boll", grid, (o, h, lo, c), 98280)
@@ -110,9 +111,9 @@ def test_ema_split_equals_unsplit_and_oracle(segments, burn, long_window, stage)
     the speculative chains meet the true ones; with a 1-2 tile burn-in the lanes' trade states
     (and the longest span's chain) mostly do not, and the fix pass re-walks from the true values.
     The 1,560-bar OLS window puts the split kernel in 128-bar stages (config 3's 250-symbol
-    shard runs so), the 780-bar one in 64-bar stages (tests/helpers.py ema_stage_tiles)."""
+    shard runs so), the 780-bar one in 64-bar stages (helpers.launch_plan: the library's planner)."""
     grid = D.Grid.ema_ols([10, 60, 390], [15, 120, long_window], band_bps=20)
-    assert ema_stage_tiles(*grid.axes[:2])[0] == stage
+    assert launch_plan(grid)["ts"] == stage
     cols = [F.gen(0x5EED, 60 + i, 40000, 1) for i in range(3)]
     ref, used1, _ = _run_grid(grid, cols, 1)
     got, used, refixed = _run_grid(grid, cols, segments, burn)
@@ -129,7 +130,7 @@ def test_ema_split_equals_unsplit_and_oracle(segments, burn, long_window, stage)
 @pytest.mark.parametrize("long_window,stage", [(200, 1), (1700, 2)])
 def test_ema_split_ragged_and_empty_segments(long_window, stage):
     grid = D.Grid.ema_ols([2, 3, 10, 100], [2, 4, 70, long_window], band_bps=20)
-    assert ema_stage_tiles(*grid.axes[:2])[0] == stage
+    assert launch_plan(grid)["ts"] == stage
     lengths = [1, 2, 63, 64, 65, 130, 700, 5000]
     cols = [F.gen(0x5EED, 80 + i, n, 1) for i, n in enumerate(lengths)]
     ref, _, _ = _run_grid(grid, cols, 1)
@@ -173,7 +174,7 @@ def test_ema_auto_split_config3_grid_small_shard():
         e.run()
         got = e.summaries().copy()
         used, refixed = e.last_segments(with_refixed=True)
-    assert used >= 2
+    assert used >= 2 and used == launch_plan(grid, 100, 98280, cus=gpu_cus())["G"]
     print(f"config-3 grid, 100 symbols: {used} segments, {refixed} boundary blocks re-walked")
     for s in (0, 63, 99):
         o, h, lo, c = F.gen(0x5EED, 200 + s, 98280, 1)[:4]
@@ -245,11 +246,11 @@ def test_sma_auto_segments_only_for_few_long_blocks():
     with D.Engine(D.config2_grid()) as e:
         e.load_synthetic(0x5EED, 0, 600, 2520, D.BT_DAILY)
         e.run()
-        assert e.last_segments() == 1
+        assert e.last_segments() == 1 == launch_plan(D.config2_grid(), 600, 2520, cus=gpu_cus())["G"]
     with D.Engine(D.config5_grid()) as e:
         e.load_synthetic(0x5EED, 0, 300, 60000, D.BT_MINUTE)
         e.run()
-        assert e.last_segments() > 1
+        assert 1 < e.last_segments() == launch_plan(D.config5_grid(), 300, 60000, cus=gpu_cus())["G"]
         got = e.summaries().copy()
     closes = np.stack([F.gen(0x5EED, s, 60000, 1)[3] for s in (0, 299)])
     grid = D.config5_grid()

@@ -25,7 +25,7 @@ import pytest
 
 import dbx_amd as D
 import orc_ffi as F
-from helpers import compare_summary, compare_trades, oracle_row
+from helpers import compare_summary, compare_trades, launch_plan, oracle_row
 
 SEED = 0x7121
 ANN = 252
@@ -138,12 +138,10 @@ def test_warm_up_skip_gpu(kind, mode):
 
 
 # ------------------------------------------------------------------------------- ring mirror
-def _ring_len(wmax):
-    """engine.cpp validate_and_copy, BT_SMA_CROSS: next_pow2(wmax + 3 * kTile)."""
-    r = 1
-    while r < wmax + 3 * 64:
-        r <<= 1
-    return r
+def _planned_ring(wmax):
+    """The SMA prefix ring of a grid whose longest window is wmax, from the library's planner
+    (plan.cpp plan_grid through helpers.launch_plan)."""
+    return launch_plan(_ring_grid(wmax))["ring"]
 
 
 # the largest wmax of a 256-entry ring and of a 512-entry ring, and one more each
@@ -160,19 +158,19 @@ def _ring_grid(wmax):
 def _ring_case(name):
     wmax = RING_WMAX[name]
     grid = _ring_grid(wmax)
-    n = 3 * _ring_len(wmax) + 77       # every ring position is overwritten at least 3 times
+    n = 3 * _planned_ring(wmax) + 77       # every ring position is overwritten at least 3 times
     series = [_walk(11, n), _const(n), _zigzag(n), _walk(12, n + 51)]   # n + 51: whole tiles
     return grid, series, _oracle(grid, series, CAP_RING)
 
 
 def test_ring_grids_sit_on_the_sizing_rule():
-    assert [_ring_len(w) for w in (64, 65, 320, 321)] == [256, 512, 512, 1024]
+    assert [_planned_ring(w) for w in (64, 65, 320, 321)] == [256, 512, 512, 1024]
     for name, wmax in RING_WMAX.items():
         grid, series, oracle = _ring_case(name)
-        assert max(grid.axes[1]) == wmax and _ring_len(wmax) == int(name[1:name.index("_")])
+        assert max(grid.axes[1]) == wmax and _planned_ring(wmax) == int(name[1:name.index("_")])
         windows = set(grid.axes[0]) | set(grid.axes[1])
         assert 3 in windows and {63, 64, 65} & windows and (wmax < 66 or {63, 64, 65} <= windows)
-        assert all(3 * _ring_len(wmax) <= len(c) <= 3500 for c in series)
+        assert all(3 * _planned_ring(wmax) <= len(c) <= 3500 for c in series)
         assert len(series[3]) % 64 == 0
         _no_trades_on_constant([oracle[1]])
         assert max(int(o["n_trades"]) for o in oracle[2][0]) <= CAP_RING
@@ -205,14 +203,10 @@ SPARSE_BARS = (333, 448)
 CAP_SPARSE = 448
 
 
-def _sma_shape(P):
-    """k_sma.hip sma_shape: parameter waves per block and y-blocks per symbol."""
-    need = (P + 63) // 64
-    if need == 16:
-        return 16, 1
-    nby = (need + 14) // 15
-    pw = (need + nby - 1) // nby
-    return pw, (P + 64 * pw - 1) // (64 * pw)
+def _sma_shape(grid):
+    """Parameter waves per block and y-blocks per symbol, from the library's planner."""
+    p = launch_plan(grid)
+    return p["block"] // 64 - p["dedicated"], p["grid_y"]
 
 
 def _sparse_pairs(fast, slow):
@@ -242,7 +236,7 @@ def _sparse_case(name):
 def test_sparse_grid_shapes(name):
     fast, slow = (list(x) for x in SPARSE_GRIDS[name])
     P = len(fast) * len(slow)
-    pw, gy = _sma_shape(P)
+    pw, gy = _sma_shape(D.Grid.sma(fast, slow))
     pairs = _sparse_pairs(fast, slow)
     assert len(pairs) == SPARSE_LIVE[name] == (P - 1) % 64 + 1
     if name == "p16":

@@ -8,7 +8,7 @@ parity cases must hold both shapes often:
   tile (the non-first, merge-free walk iterations).
 
 EMA+OLS runs 128-bar stages (two tiles per barrier) when they keep as many blocks per CU as
-64-bar ones (`k_tile.hip ema_stage_tiles`): a long OLS window (1,560 bars, config 3's) puts the
+64-bar ones (`plan.cpp ema_stage_tiles`): a long OLS window (1,560 bars, config 3's) puts the
 `ema_ols_128` grid there, and its cases must also hold trades carried across a stage edge, exits
 on a stage's first bar, entries on a stage's last bar and trades across the edge between a
 stage's two tiles.
@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 import dbx_amd as D
-from helpers import compare_summary, compare_trades, ema_stage_tiles, oracle_row
+from helpers import compare_summary, compare_trades, launch_plan, oracle_row
 
 CAP = 8192
 T = 64
@@ -79,15 +79,20 @@ def _stage_shapes(trades, n, S=2 * T):
 
 
 def test_stage_model_picks_the_kernels_shapes():
-    """helpers.ema_stage_tiles mirrors the launcher's rule: config 3's block is 61,120 B at 64-bar
-    and 80,208 B at 128-bar stages (k_tile.hip ema_stage_tiles), two per CU either way."""
-    g3 = D.config3_grid()
-    assert ema_stage_tiles(g3.axes[0], g3.axes[1]) == (2, 61120, 80208)
+    """The planner's own rule (plan.cpp ema_stage_tiles over lds_layout.h tile_lds_layout, asked
+    through helpers.launch_plan): config 3's block is 61,120 B at 64-bar and 80,208 B at 128-bar
+    stages, two per CU either way."""
+    def stage(grid):
+        p = launch_plan(grid)
+        assert p["lds"] == p["ema_lds"][p["ts"] - 1]
+        return (p["ts"], *p["ema_lds"])
+
+    assert stage(D.config3_grid()) == (2, 61120, 80208)
     # test_ema_stage_shapes' two cases: one of each shape
-    assert ema_stage_tiles([10, 780], [1560, 15]) == (1, 54288, 66560)
-    assert ema_stage_tiles([10, 780], [1700, 30]) == (2, 56336, 68608)
-    assert ema_stage_tiles(*GRIDS["ema_ols_128"]().axes[:2])[0] == 2
-    assert ema_stage_tiles(*GRIDS["ema_ols"]().axes[:2])[0] == 1
+    assert stage(D.Grid.ema_ols([10, 780], [1560, 15])) == (1, 54288, 66560)
+    assert stage(D.Grid.ema_ols([10, 780], [1700, 30])) == (2, 56336, 68608)
+    assert stage(GRIDS["ema_ols_128"]())[0] == 2
+    assert stage(GRIDS["ema_ols"]())[0] == 1
 
 
 def test_cases_hold_stage_edge_shapes():
