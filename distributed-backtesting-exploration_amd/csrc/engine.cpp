@@ -24,6 +24,7 @@
 #include "csv.h"
 #include "internal.h"
 #include "plan.h"
+#include "surface.h"
 
 using namespace bt;
 
@@ -140,6 +141,12 @@ struct bt_engine {
     // bt_replay: device staging of one chunk of requests (descriptors, summaries, trades, curves),
     // at most kReplayBudget bytes whatever n and stride are
     DevBuf<uint8_t> d_replay;
+    // bt_surface: requested row chunks (0 = the planner's choice), the partials and results of
+    // one reduction, and the matrix and ids bt_surface_of stages
+    int32_t surface_chunks = 0;
+    DevBuf<uint8_t> d_surface, d_surface_in;
+    uint8_t* h_surface = nullptr;  // pinned: the results of one reduction
+    size_t h_surface_n = 0;
 };
 
 namespace {
@@ -465,6 +472,76 @@ int32_t replay_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade
     if (n_bars)
         for (int32_t i = 0; i < n; ++i) n_bars[i] = req[i].bars;
     return n;
+}
+
+// ---- bt_surface / bt_surface_of: the run's summaries reduced on the device (k_surface.hip)
+// `d_sum` and `d_ids` are device pointers the engine's streams have finished writing; the pass and
+// its folds run on the engine stream and the results are copied back before the call returns.
+void surface_launch(bt_engine* e, const bt_summary* d_sum, const int32_t* d_ids, int32_t id_stride,
+                    int32_t S, int32_t P, bt_param_agg* agg, bt_topk_rec* best) {
+    const SurfacePlan pl = plan_surface(S, P, e->cus, e->surface_chunks);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_part = 0, o_fold = o_part + up(pl.partial_bytes);
+    const size_t o_bpart = o_fold + up(pl.fold_bytes);
+    const size_t o_agg = o_bpart + up(pl.best_partial_bytes);
+    const size_t o_best = o_agg + up((size_t)P * sizeof(bt_param_agg));
+    e->d_surface.ensure(o_best + up((size_t)S * sizeof(bt_topk_rec)) + 256);
+    uint8_t* base = e->d_surface.p;
+    SurfaceWork w{};
+    w.partial = reinterpret_cast<bt_param_agg*>(base + o_part);
+    w.fold = reinterpret_cast<bt_param_agg*>(base + o_fold);
+    w.best_partial = reinterpret_cast<bt_topk_rec*>(base + o_bpart);
+    w.agg = agg ? reinterpret_cast<bt_param_agg*>(base + o_agg) : nullptr;
+    w.best = best ? reinterpret_cast<bt_topk_rec*>(base + o_best) : nullptr;
+    HIPCHK(launch_surface(d_sum, d_ids, id_stride, S, P, pl, w, e->stream));
+    // the results lie next to each other: one copy into pinned memory, whatever was asked for
+    const size_t n_agg = (size_t)P * sizeof(bt_param_agg), n_best = (size_t)S * sizeof(bt_topk_rec);
+    const size_t lo = agg ? o_agg : o_best, hi = best && S > 0 ? o_best + n_best : o_agg + n_agg;
+    if (hi <= lo) return;  // best alone of a matrix without rows
+    ensure_pinned(e->h_surface, e->h_surface_n, hi - lo);
+    HIPCHK(hipMemcpyAsync(e->h_surface, base + lo, hi - lo, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (agg) memcpy(agg, e->h_surface + (o_agg - lo), n_agg);
+    if (best && S > 0) memcpy(best, e->h_surface + (o_best - lo), n_best);
+}
+
+int32_t surface_impl(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
+    auto refuse = [](const std::string& m) { throw HipFail{"bt_surface: " + m}; };
+    if (!e) refuse("null engine");
+    if (!e->ran) refuse("no results");
+    uint64_t rows = 0;
+    for (const SymDesc& sd : e->syms) rows += (uint64_t)sd.bars;
+    const std::string why = surface_refusal((int64_t)e->syms.size(), e->P, agg || best, false, rows);
+    if (!why.empty()) refuse(why);
+    activate(e);
+    sync_all(e);
+    // ids straight from the symbol descriptors: SymDesc is four int32 wide, the id its last
+    static_assert(sizeof(SymDesc) == 16 && offsetof(SymDesc, id) == 12, "SymDesc layout");
+    surface_launch(e, e->d_sum[e->cur].p, reinterpret_cast<const int32_t*>(e->d_syms.p) + 3, 4,
+                   (int32_t)e->syms.size(), e->P, agg, best);
+    return 0;
+}
+
+int32_t surface_of_impl(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* ids,
+                        bt_param_agg* agg, bt_topk_rec* best) {
+    auto refuse = [](const std::string& m) { throw HipFail{"bt_surface_of: " + m}; };
+    if (!e) refuse("null engine");
+    const std::string why = surface_refusal(S, P, agg || best, true, 0);
+    if (!why.empty()) refuse(why);
+    if (S > 0 && (!sum || !ids)) refuse("sum and sym_ids are required");
+    activate(e);
+    sync_all(e);
+    const size_t n = (size_t)S * (size_t)P;
+    const size_t o_ids = (n * sizeof(bt_summary) + 255) & ~(size_t)255;
+    e->d_surface_in.ensure(o_ids + (size_t)S * sizeof(int32_t) + 256);
+    uint8_t* base = e->d_surface_in.p;
+    if (n) {
+        HIPCHK(hipMemcpyAsync(base, sum, n * sizeof(bt_summary), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(base + o_ids, ids, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    }
+    surface_launch(e, reinterpret_cast<const bt_summary*>(base), reinterpret_cast<const int32_t*>(base + o_ids),
+                   1, S, P, agg, best);
+    return 0;
 }
 
 void drain_timing(bt_engine* e) {
@@ -874,6 +951,10 @@ void bt_engine_destroy(bt_engine* e) {
         e->d_refixed.release();
         e->d_dbg.release();
         e->d_replay.release();
+        e->d_surface.release();
+        e->d_surface_in.release();
+        if (e->h_surface) (void)hipHostFree(e->h_surface);
+        e->h_surface = nullptr;
         e->d_hist.release();
         e->d_counts.release();
         e->d_state.release();
@@ -1119,6 +1200,24 @@ int32_t bt_read_close(bt_engine* e, int32_t sym_index, int32_t* out, int32_t n) 
 int32_t bt_replay(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
                   int32_t* n_bars, bt_trade* trades, int64_t* equity, int8_t* pos, int64_t stride) {
     ABI_GUARD(-1, { return replay_impl(e, n, lanes, trade_cap, sum, n_bars, trades, equity, pos, stride); })
+}
+
+int32_t bt_surface(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
+    ABI_GUARD(-1, { return surface_impl(e, agg, best); })
+}
+
+int32_t bt_surface_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* sym_ids,
+                      bt_param_agg* agg, bt_topk_rec* best) {
+    ABI_GUARD(-1, { return surface_of_impl(e, S, P, sum, sym_ids, agg, best); })
+}
+
+int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks) {
+    ABI_GUARD(-1, {
+        if (!e) throw HipFail{"bt_set_surface_chunks: null engine"};
+        if (chunks < 0) throw HipFail{"bt_set_surface_chunks: chunks = " + std::to_string(chunks) + " is negative"};
+        e->surface_chunks = chunks;
+        return 0;
+    })
 }
 
 int32_t bt_read_debug(bt_engine* e, uint64_t* out, int32_t n) {

@@ -164,6 +164,21 @@ struct ReplayOut {
 hipError_t launch_replay(const ReplayLane* lanes, int32_t n, const int32_t* high, const int32_t* low,
                          const int32_t* close, const Grid& g, const ReplayOut& o, hipStream_t st);
 
+// Reductions of an S x P summary matrix (k_surface.hip, bt_surface / bt_surface_of): one pass over
+// the records writes per-chunk column aggregates and per-tile row winners, two short kernels fold
+// them into agg[P] and best[S]. Symbol s has id ids[s * id_stride] (the engine's SymDesc array or
+// a plain id list). Either output may be nullptr; the shape is the SurfacePlan's (plan.h).
+struct SurfacePlan;
+struct SurfaceWork {
+    bt_param_agg* partial;         // [chunks * P]
+    bt_param_agg* fold;            // [fold_ways * P]: the first fold step's output
+    bt_topk_rec* best_partial;     // [S * p_tiles]
+    bt_param_agg* agg;             // [P] or nullptr
+    bt_topk_rec* best;             // [S] or nullptr
+};
+hipError_t launch_surface(const bt_summary* sum, const int32_t* ids, int32_t id_stride, int32_t S,
+                          int32_t P, const SurfacePlan& pl, const SurfaceWork& w, hipStream_t st);
+
 // Top-k by radix select over `key` (k_topk.hip): device-side finish into `out`.
 constexpr int kTopkCap = 2048;      // candidates sorted in LDS by the finish kernel
 constexpr int kTopkMax = 1024;      // largest k the engine accepts

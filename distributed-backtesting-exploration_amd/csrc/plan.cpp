@@ -359,4 +359,39 @@ LaunchPlan plan_launch(const Grid& g, const int32_t* ax0, const RunShape& r) {
     return pl;
 }
 
+// ---------------------------------------------------------------------------- run reductions
+// The pass is a read-once stream of 48-B records, so it wants the whole GPU whatever P is
+// (config 3 has one 64-lane tile per row): the rows are cut into enough chunks for
+// kSurfaceWaves waves per SIMD. Every chunk writes one 104-B partial per parameter, a little more
+// than two records' worth, so a chunk keeps at least kSurfaceMinRows rows (partials then add at most
+// 104 / (16 x 48) = 14 % to the bytes moved) even when that leaves fewer waves.
+SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req) {
+    constexpr int kSurfaceWaves = 4, kSurfaceMinRows = 16;
+    constexpr int32_t kMaxGridY = 65535;
+    SurfacePlan pl{};
+    S = std::max(S, 0);
+    P = std::max(P, 1);
+    pl.p_tiles = (P + 63) / 64;
+    pl.block = 64 * std::min(pl.p_tiles, 4);
+    pl.p_blocks = (P + pl.block - 1) / pl.block;
+    int64_t chunks = chunks_req;
+    if (chunks <= 0) {
+        const int64_t waves_per_chunk = (int64_t)pl.p_blocks * (pl.block / 64);
+        const int64_t want = ((int64_t)std::max(cus, 1) * 4 * kSurfaceWaves + waves_per_chunk - 1) / waves_per_chunk;
+        chunks = std::min<int64_t>(want, S / kSurfaceMinRows);
+    }
+    chunks = std::max<int64_t>(1, std::min<int64_t>(chunks, std::min<int64_t>(S, kMaxGridY)));
+    pl.chunks = (int32_t)chunks;
+    pl.rows_per_chunk = S / pl.chunks;
+    pl.rows_rem = S % pl.chunks;
+    // the fold walks its partials one after the other (a merge has branches): past kFoldDirect
+    // chunks it is cut into ~sqrt(chunks) interleaved walks whose results a second step merges
+    constexpr int kFoldDirect = 16;
+    if (pl.chunks > kFoldDirect) pl.fold_ways = (int32_t)std::ceil(std::sqrt((double)pl.chunks));
+    pl.partial_bytes = (size_t)pl.chunks * (size_t)P * sizeof(bt_param_agg);
+    pl.fold_bytes = (size_t)pl.fold_ways * (size_t)P * sizeof(bt_param_agg);
+    pl.best_partial_bytes = (size_t)S * (size_t)pl.p_tiles * sizeof(bt_topk_rec);
+    return pl;
+}
+
 }  // namespace bt

@@ -54,4 +54,22 @@ struct RunShape {
 // `ax0`: the host copy of the grid's first axis (Grid::a; the EMA burn-in follows its spans).
 LaunchPlan plan_launch(const Grid& g, const int32_t* ax0, const RunShape& r);
 
+// What a reduction of an S x P summary matrix is launched with (k_surface.hip launch_surface).
+// Lanes run along p: grid x tiles the parameters in blocks of `block` threads, grid y cuts the
+// rows into `chunks`. Chunk c holds rows_per_chunk + (c < rows_rem) rows, starting at row
+// c * rows_per_chunk + min(c, rows_rem): every row exactly once, no chunk empty while S > 0.
+struct SurfacePlan {
+    int32_t block;                 // threads per block of the pass kernel (a multiple of 64)
+    int32_t p_blocks;              // blocks along p
+    int32_t chunks;                // row chunks (1 with no rows)
+    int32_t rows_per_chunk, rows_rem;
+    int32_t p_tiles;               // 64-lane tiles of a row: per-row best partials
+    int32_t fold_ways;             // partials left by the first of two fold steps (0: one step)
+    size_t partial_bytes;          // chunk aggregates: chunks x P bt_param_agg
+    size_t fold_bytes;             // the first fold step's output: fold_ways x P bt_param_agg
+    size_t best_partial_bytes;     // tile winners: S x p_tiles bt_topk_rec
+};
+// `chunks_req`: bt_set_surface_chunks (0 = automatic).
+SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req);
+
 }  // namespace bt

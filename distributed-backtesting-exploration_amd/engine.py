@@ -46,6 +46,15 @@ LANE_DTYPE = np.dtype([("sym", "<i4"), ("param", "<i4")])  # include/bt.h bt_lan
 REPLAY_MAX = 4096  # include/bt.h BT_REPLAY_MAX: lanes per Engine.replay call
 assert SUMMARY_DTYPE.itemsize == 48 and TOPK_DTYPE.itemsize == 24 and TRADE_DTYPE.itemsize == 32
 assert LANE_DTYPE.itemsize == 8
+# include/bt.h bt_param_agg: one parameter's aggregate over every symbol (docs/surface_spec.md)
+PARAM_AGG_DTYPE = np.dtype([
+    ("n_sym", "<i4"), ("n_traded", "<i4"), ("n_win", "<i4"), ("n_pos", "<i4"),
+    ("trades", "<i8"), ("pnl", "<i8"), ("exposure", "<i8"), ("mdd_max", "<i8"),
+    ("sharpe_max", "<f8"), ("sharpe_min", "<f8"), ("sym_max", "<i4"), ("sym_min", "<i4"),
+    ("ss1_lo", "<u8"), ("ss1_hi", "<i8"), ("ss2_lo", "<u8"), ("ss2_hi", "<i8"),
+])
+assert PARAM_AGG_DTYPE.itemsize == 104
+SURFACE_OF_MAX = 1 << 22  # records Engine.surface_of stages (include/bt.h bt_surface_of)
 
 
 class BtError(RuntimeError):
@@ -184,6 +193,13 @@ _LATE_SYMBOLS = {
                               C.c_void_p], C.c_int32),
     "bt_replay": (3, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64], C.c_int32),
+    "bt_surface": (3, [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_surface_of": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_void_p], C.c_int32),
+    "bt_set_surface_chunks": (3, [C.c_void_p, C.c_int32], C.c_int32),
+    "bt_surface_host": (3, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                        C.c_int32),
+    "bt_surface_merge": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], C.c_int32),
 }
 _late = {}
 
@@ -328,6 +344,91 @@ class Replay:
     trades: np.ndarray | None   # TRADE_DTYPE[n, trade_cap]: the first trades, then zeros
     equity: np.ndarray | None   # int64[n, max bars]: E_t (spec §4), zero past the symbol's bars
     pos: np.ndarray | None      # int8[n, max bars]: position after bar t
+
+
+@dataclass
+class Surface:
+    """A run reduced along each axis (bt_surface, docs/surface_spec.md): one aggregate per
+    parameter over every symbol, and each symbol's best lane in dataset row order."""
+    params: np.ndarray            # PARAM_AGG_DTYPE[P]
+    best: np.ndarray | None       # TOPK_DTYPE[S] (feeds Engine.replay), or None when not asked for
+
+    def _sum128(self, name) -> np.ndarray:
+        return np.array([i128_to_double(int(r[name + "_lo"]), int(r[name + "_hi"])) for r in self.params],
+                        np.float64)
+
+    def mean_sharpe(self) -> np.ndarray:
+        """Mean over the symbols of the clamped fixed-point Sharpe (0.0 where n_sym == 0)."""
+        n = self.params["n_sym"].astype(np.float64)
+        return np.divide(self._sum128("ss1") / 2.0**32, n, out=np.zeros(len(n)), where=n > 0)
+
+    def std_sharpe(self) -> np.ndarray:
+        """Population standard deviation of the same, from ss1 and ss2."""
+        n = self.params["n_sym"].astype(np.float64)
+        m2 = np.divide(self._sum128("ss2") / 2.0**64, n, out=np.zeros(len(n)), where=n > 0)
+        return np.sqrt(np.maximum(m2 - self.mean_sharpe() ** 2, 0.0))
+
+    def win_rate(self) -> np.ndarray:
+        """Share of the symbols with pnl > 0."""
+        n = self.params["n_sym"].astype(np.float64)
+        return np.divide(self.params["n_win"].astype(np.float64), n, out=np.zeros(len(n)), where=n > 0)
+
+    def rank(self, k=None, by="mean_sharpe") -> np.ndarray:
+        """Parameter indices, best (largest `by`) first, ties to the lower index; Grid.param
+        decodes them. `by`: mean_sharpe, std_sharpe, win_rate or a numeric field of `params`."""
+        derived = {"mean_sharpe": self.mean_sharpe, "std_sharpe": self.std_sharpe, "win_rate": self.win_rate}
+        if by in derived:
+            v = derived[by]()
+        elif by in (self.params.dtype.names or ()):
+            v = self.params[by]
+        else:
+            raise ValueError(f"rank by {by!r}: one of {sorted(derived)} or a field of PARAM_AGG_DTYPE")
+        # descending and stable without negating (int64 minima, unsigned fields)
+        order = (len(v) - 1 - np.argsort(v[::-1], kind="stable"))[::-1]
+        return order if k is None else order[:k]
+
+
+def _surface_bufs(S, P, best):
+    agg = np.zeros(max(P, 1), PARAM_AGG_DTYPE)
+    rec = np.zeros(max(S, 1), TOPK_DTYPE) if best else None
+    return agg, rec
+
+
+def _as_matrix(summaries, sym_ids):
+    m = np.ascontiguousarray(summaries, SUMMARY_DTYPE)
+    if m.ndim != 2:
+        raise ValueError("summaries: an S x P array of SUMMARY_DTYPE")
+    ids = np.ascontiguousarray(np.asarray(sym_ids, np.int32))
+    if ids.shape != (m.shape[0],):
+        raise ValueError(f"sym_ids: {m.shape[0]} ids for {m.shape[0]} rows, got shape {ids.shape}")
+    return m, ids
+
+
+def surface_host(summaries, sym_ids, best=True) -> Surface:
+    """bt_surface_host: the reductions of an S x P summary matrix on the CPU (no GPU needed)."""
+    m, ids = _as_matrix(summaries, sym_ids)
+    S, P = m.shape
+    agg, rec = _surface_bufs(S, P, best)
+    _check(sym("bt_surface_host")(S, P, m.ctypes.data if m.size else None, ids.ctypes.data if S else None,
+                                  agg.ctypes.data, None if rec is None else rec.ctypes.data))
+    return Surface(agg[:P], None if rec is None else rec[:S])
+
+
+def merge_surfaces(parts) -> Surface:
+    """bt_surface_merge: surfaces of disjoint symbol sets (shards, ranks) as one. The per-symbol
+    records are concatenated in the order given."""
+    parts = list(parts)
+    world = len(parts)
+    P = len(parts[0].params) if parts else 0
+    if any(len(s.params) != P for s in parts):
+        raise ValueError("merge_surfaces: the surfaces hold different parameter counts")
+    block = (np.ascontiguousarray(np.concatenate([s.params for s in parts]), PARAM_AGG_DTYPE) if parts
+             else np.zeros(1, PARAM_AGG_DTYPE))
+    out = np.zeros(max(P, 1), PARAM_AGG_DTYPE)
+    _check(sym("bt_surface_merge")(block.ctypes.data, world, P, out.ctypes.data))
+    best = (np.concatenate([s.best for s in parts]) if parts and all(s.best is not None for s in parts)
+            else None)
+    return Surface(out[:P], best)
 
 
 class Engine:
@@ -490,6 +591,32 @@ class Engine:
         _check(f(self._h, len(req), req.ctypes.data, 0, summ.ctypes.data, nb.ctypes.data, None, None,
                  None, 0))
         return int(nb.max())
+
+    # ---- reductions of the last run (bt_surface, k_surface.hip)
+    def surface(self, best: bool = True) -> Surface:
+        """The last run (run() or run_batch()) reduced on the GPU: one aggregate per parameter
+        over every symbol and, with best, each symbol's best lane in dataset row order."""
+        f = sym("bt_surface")
+        S = self.stats()["n_symbols"]
+        agg, rec = _surface_bufs(S, self.n_params, best)
+        _check(f(self._h, agg.ctypes.data, None if rec is None else rec.ctypes.data))
+        return Surface(agg[:self.n_params], None if rec is None else rec[:S])
+
+    def surface_of(self, summaries, sym_ids, best: bool = True) -> Surface:
+        """The same device kernels on a caller's S x P summary matrix (at most SURFACE_OF_MAX
+        records) and its symbol ids."""
+        m, ids = _as_matrix(summaries, sym_ids)
+        S, P = m.shape
+        agg, rec = _surface_bufs(S, P, best)
+        _check(sym("bt_surface_of")(self._h, S, P, m.ctypes.data if m.size else None,
+                                    ids.ctypes.data if S else None, agg.ctypes.data,
+                                    None if rec is None else rec.ctypes.data))
+        return Surface(agg[:P], None if rec is None else rec[:S])
+
+    def set_surface_chunks(self, n: int) -> None:
+        """Symbol chunks surface() cuts the rows into: 0 = the planner's choice, n = always n
+        (clipped to the symbol count). Results are identical either way."""
+        _check(sym("bt_set_surface_chunks")(self._h, n))
 
     def stats(self) -> dict:
         st = _Stats()

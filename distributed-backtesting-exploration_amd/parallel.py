@@ -46,6 +46,22 @@ def gather_topk(local: np.ndarray, k: int, dist) -> np.ndarray:
     return merge_topk(np.concatenate(parts) if parts else np.zeros(0, TOPK_DTYPE), k)
 
 
+def gather_surface(local, dist):
+    """All-gather every rank's per-parameter aggregates (Surface.params, P x 104 B) and merge
+    them with bt_surface_merge: the surface of the whole symbol universe, identical on every rank
+    and identical to a single engine's (docs/surface_spec.md §3). The per-symbol records are not
+    exchanged: the result's `best` is this rank's own."""
+    import torch
+    from .engine import PARAM_AGG_DTYPE, Surface, merge_surfaces
+    world = dist.get_world_size()
+    mine = np.ascontiguousarray(local.params, PARAM_AGG_DTYPE)
+    t = torch.from_numpy(mine.view(np.uint8).copy()).to(_device_for(dist))
+    out = torch.empty(world * t.numel(), dtype=torch.uint8, device=t.device)
+    dist.all_gather_into_tensor(out, t)
+    blocks = out.cpu().numpy().view(PARAM_AGG_DTYPE).reshape(world, len(mine))
+    return Surface(merge_surfaces([Surface(b, None) for b in blocks]).params, local.best)
+
+
 def exchange(local: np.ndarray, k: int, counters, dist) -> tuple:
     """The whole per-step exchange as ONE all-gather of the byte message bt_exchange_async sends
     over RCCL (csrc/comm.cpp: [header record with the count | k records | bar-evals | trades]),

@@ -233,6 +233,43 @@ int32_t bt_replay(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_c
                   int64_t* equity,    /* [n * stride] or NULL */
                   int8_t* pos,        /* [n * stride] or NULL */
                   int64_t stride);    /* >= the longest requested symbol when equity or pos is given */
+/* ---- reductions of a run (k_surface.hip, surface.cpp; semantics: docs/surface_spec.md)
+ * The S x P summaries a run leaves in HBM, reduced along each axis on the device:
+ *   agg[p]   one bt_param_agg per parameter over every row with status == 0 (the "parameter
+ *            surface"): counts, int64 sums, the worst drawdown, the fixed-point Sharpe sums
+ *            ss1 = sum qs, ss2 = sum qs^2 (int128 as lo/hi words like bt_sums,
+ *            qs = rint(clamp(sharpe, +-2^15) * 2^32)), and the best and worst symbol;
+ *   best[s]  one bt_topk_rec per dataset row, in row order: the row's first lane in the top-k
+ *            order (Sharpe descending, then param ascending), sym = the global id. Feeds bt_replay.
+ * Every field is order-independent: any chunking and any split over ranks gives the same bits.
+ * Added within ABI 3 (additive). */
+typedef struct bt_param_agg {           /* 104 bytes */
+    int32_t n_sym, n_traded, n_win, n_pos;   /* rows counted; with n_trades > 0, pnl > 0, sharpe > 0 */
+    int64_t trades, pnl, exposure, mdd_max;  /* sums; the largest mdd (0 when n_sym == 0) */
+    double  sharpe_max, sharpe_min;          /* 0.0 when n_sym == 0 */
+    int32_t sym_max, sym_min;                /* their symbols' ids, ties to the lowest; -1 when n_sym == 0 */
+    uint64_t ss1_lo; int64_t ss1_hi; uint64_t ss2_lo; int64_t ss2_hi;
+} bt_param_agg;
+
+/* Reduce the last run's summaries on the device. agg[P] and/or best[S] (either may be NULL, not
+ * both). Synchronous like bt_replay: waits for the engine's streams, runs on the engine stream,
+ * copies back; changes nothing another entry point reads. Works after bt_run and bt_run_batch.
+ * Returns 0, or -1 with bt_last_error naming the offending value (the engine stays usable): a null
+ * engine, no run yet, both outputs NULL, a dataset of 2^32 rows or more (the int64 sums are exact
+ * only below that and are never wrapped). */
+int32_t bt_surface(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best);
+/* The same device kernels on a caller's matrix (row-major S x P, sym_ids[S]); S*P <= 2^22. S == 0
+ * gives P empty aggregates and no best record; S < 0 or P < 1 is refused. */
+int32_t bt_surface_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum,
+                      const int32_t* sym_ids, bt_param_agg* agg, bt_topk_rec* best);
+/* Symbol chunks the reduction is cut into: 0 = the planner's choice, n = always n (clipped to S).
+ * Results are identical either way. */
+int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks);
+/* Host, no GPU needed: the scalar restatement, and the merge of `world` aggregates of P records
+ * (in[w * P + p], disjoint symbol sets; world >= 1) into out[P]. */
+int32_t bt_surface_host(int32_t S, int32_t P, const bt_summary* sum, const int32_t* sym_ids,
+                        bt_param_agg* agg, bt_topk_rec* best);
+int32_t bt_surface_merge(const bt_param_agg* in, int32_t world, int32_t P, bt_param_agg* out);
 /* Average device time of the dominant kernel (BT_FLAG_TIMING), and how many launches. */
 int32_t bt_kernel_timing(bt_engine* e, double* total_ms, int64_t* launches, const char** name);
 int32_t bt_reset_timing(bt_engine* e);
