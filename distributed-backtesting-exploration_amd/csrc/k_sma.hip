@@ -19,8 +19,9 @@
 //            sign bit is shifted into the 64-bit word L (fast key < slow key), and a running
 //            unsigned min that detects equal keys; without equal keys G (fast > slow) = ~L.
 //            Keys are monotone in the exact SMA, so a strict key order is the exact order; equal
-//            keys (rare: ~1e-4 of lane-tiles on config 2) are settled exactly (F*s vs L*f in
-//            int64, products < 2^59). The whole tile's position path then follows
+//            keys (~1e-4 of lane-tiles on config 2, far more on config 5's minute bars) are
+//            found by a second pass over the two rows (eq_word) and settled exactly (F*s vs L*f
+//            in int64, products < 2^59). The whole tile's position path then follows
 //            bit-parallel: a set/reset latch is an add-with-carry (LONG = carries of
 //            ~L + G + [pos == +1]). Each lane walks only its flips (ctz): per trade O(1) work —
 //            PnL, MTM drawdown from the DST, Sharpe sums as int128 prefix differences, hash.
@@ -229,12 +230,29 @@ __device__ __forceinline__ void cmp4(uint32_t& l, uint32_t& z, const int4& x, co
     z = min(min(z, d2), d3);
 }
 
-// Equality word for the rare tiles with equal keys (same bit order as cmp4).
+// Equality word for the tiles with equal keys, bit b = bar b: a second pass over the two rows
+// that shifts [x == y] in as cmp4 shifts [x < y] (min(d, 1) - 1 is all ones iff d == 0), 32
+// ds_read_b128 and 4 VALU per bar. A 64-step loop of two dependent 4-byte reads per bar took a
+// lane ~6,000 cycles per tied tile while its wave waited: 3 % of config 2's kernel and 18 % of
+// config 5's shard, whose minute bars tie often.
+__device__ __forceinline__ void eq4(uint32_t& e, const int4& x, const int4& y) {
+    e = __builtin_amdgcn_alignbit(e, min((uint32_t)(x.x - y.x), 1u) - 1u, 31);
+    e = __builtin_amdgcn_alignbit(e, min((uint32_t)(x.y - y.y), 1u) - 1u, 31);
+    e = __builtin_amdgcn_alignbit(e, min((uint32_t)(x.z - y.z), 1u) - 1u, 31);
+    e = __builtin_amdgcn_alignbit(e, min((uint32_t)(x.w - y.w), 1u) - 1u, 31);
+}
 __device__ __forceinline__ uint64_t eq_word(const int32_t* k1, const int32_t* k2) {
-    uint64_t e = 0;
+    const int4* r1 = reinterpret_cast<const int4*>(k1);
+    const int4* r2 = reinterpret_cast<const int4*>(k2);
+    // a rolled loop, two int4 pairs in flight (one of each half): unrolled, the pass spilled the
+    // walk's registers in the 80-VGPR kernels
+    uint32_t e0 = 0, e1 = 0;
 #pragma unroll 1
-    for (int b = 0; b < kTile; ++b) e |= (uint64_t)(k1[b] == k2[b]) << b;
-    return e;
+    for (int v = 0; v < 8; ++v) {
+        eq4(e0, r1[v], r2[v]);
+        eq4(e1, r1[v + 8], r2[v + 8]);
+    }
+    return ((uint64_t)__builtin_bitreverse32(e1) << 32) | __builtin_bitreverse32(e0);
 }
 
 }  // namespace
