@@ -21,11 +21,13 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
 
+#include "hip_owned.h"
 #include "internal.h"
 
 using namespace bt;
@@ -34,25 +36,16 @@ struct bt_comm {
     ncclComm_t comm = nullptr;
     int32_t rank = 0, world = 1, device = 0, k = 0;
     size_t rec_bytes = 0;              // bytes one rank contributes
-    unsigned char* d_send = nullptr;   // [rec_bytes]
-    unsigned char* d_recv[BT_PIPE_SLOTS] = {};  // [world * rec_bytes] per slot
-    unsigned char* h_recv[BT_PIPE_SLOTS] = {};  // pinned
-    int64_t* h_evals[BT_PIPE_SLOTS] = {};       // pinned: this rank's bar-evals per slot
-    hipEvent_t done[BT_PIPE_SLOTS] = {};
+    DevBuf<unsigned char> d_send;                   // [rec_bytes]
+    DevBuf<unsigned char> d_recv[BT_PIPE_SLOTS];    // [world * rec_bytes] per slot
+    PinnedBuf<unsigned char> h_recv[BT_PIPE_SLOTS];
+    PinnedBuf<int64_t> h_evals[BT_PIPE_SLOTS];      // this rank's bar-evals per slot
+    Event done[BT_PIPE_SLOTS];
     bool armed[BT_PIPE_SLOTS] = {};
+    ~bt_comm();
 };
 
 namespace {
-
-struct CommFail {
-    std::string msg;
-};
-
-#define HIPCHK(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess) throw CommFail{std::string(#x) + ": " + hipGetErrorString(e_)}; \
-    } while (0)
 
 // the RCCL entry points this file calls
 struct Rccl {
@@ -89,7 +82,7 @@ const Rccl& rccl() {
         sym(r.AllGather, "ncclAllGather");
         sym(r.GetErrorString, "ncclGetErrorString");
     });
-    if (!r.why.empty()) throw CommFail{r.why};
+    if (!r.why.empty()) throw HipFail{r.why};
     return r;
 }
 
@@ -97,7 +90,7 @@ const Rccl& rccl() {
     do {                                                                                       \
         ncclResult_t r_ = (x);                                                                 \
         if (r_ != ncclSuccess)                                                                 \
-            throw CommFail{std::string(#x) + ": " + rccl().GetErrorString(r_)};               \
+            throw HipFail{std::string(#x) + ": " + rccl().GetErrorString(r_)};                \
     } while (0)
 
 // Per-rank message: header record (record count in its first int32), k records, then the two
@@ -117,7 +110,7 @@ int32_t merge_block(const unsigned char* block, int32_t world, int32_t k_msg, bt
         memcpy(&n, m, sizeof n);
         // every rank's device selection is exact whatever the ties (k_topk.hip
         // topk_finish_ties), so a tie-heavy grid exchanges like any other
-        if (n < 0) throw CommFail{"rank " + std::to_string(r) + ": bad top-k record count"};
+        if (n < 0) throw HipFail{"rank " + std::to_string(r) + ": bad top-k record count"};
         n = std::min(n, k_msg);
         const unsigned char* recs = m + sizeof(bt_topk_rec);
         for (int32_t i = 0; i < n; ++i) {  // memcpy: the block carries no alignment promise
@@ -140,51 +133,39 @@ int32_t merge_block(const unsigned char* block, int32_t world, int32_t k_msg, bt
     return (int32_t)mm;
 }
 
-void release(bt_comm* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    for (int s = 0; s < BT_PIPE_SLOTS; ++s) {
-        if (c->done[s]) (void)hipEventSynchronize(c->done[s]);
-    }
-    if (c->comm) (void)rccl().CommDestroy(c->comm);  // comm set: rccl() resolved
-    if (c->d_send) (void)hipFree(c->d_send);
-    for (int s = 0; s < BT_PIPE_SLOTS; ++s) {
-        if (c->d_recv[s]) (void)hipFree(c->d_recv[s]);
-        if (c->h_recv[s]) (void)hipHostFree(c->h_recv[s]);
-        if (c->h_evals[s]) (void)hipHostFree(c->h_evals[s]);
-        if (c->done[s]) (void)hipEventDestroy(c->done[s]);
-    }
-    delete c;
-}
-
 }  // namespace
+
+// The read-backs still in flight finish, the communicator goes, then the members.
+bt_comm::~bt_comm() {
+    (void)hipSetDevice(device);
+    for (Event& ev : done)
+        if (ev) (void)hipEventSynchronize(ev);
+    if (comm) (void)rccl().CommDestroy(comm);  // comm set: rccl() resolved
+}
 
 extern "C" {
 
 int32_t bt_comm_unique_id(uint8_t* out) {
-    try {
-        if (!out) throw CommFail{"null output"};
+    ABI_GUARD(-1, {
+        if (!out) throw HipFail{"null output"};
         ncclUniqueId id;
         NCCLCHK(rccl().GetUniqueId(&id));
         static_assert(sizeof(id) == BT_COMM_ID_BYTES, "RCCL unique id size");
         memcpy(out, &id, sizeof id);
         return 0;
-    } catch (const CommFail& f) {
-        set_last_error(f.msg);
-        return -1;
-    } catch (...) {
-        set_last_error("unknown exception");
-        return -1;
-    }
+    })
 }
 
 bt_comm* bt_comm_create(const uint8_t* id, int32_t rank, int32_t world, int32_t device,
                         int32_t k, char* err, size_t errlen) {
-    bt_comm* c = nullptr;
-    try {
+    auto failed = [&]() -> bt_comm* {  // bt_last_error() into the caller's buffer too
+        if (err && errlen) snprintf(err, errlen, "%s", bt_last_error());
+        return nullptr;
+    };
+    ABI_GUARD(failed(), {
         if (!id || world < 1 || rank < 0 || rank >= world || k < 1 || k > 1024)
-            throw CommFail{"bad arguments"};
-        c = new bt_comm();
+            throw HipFail{"bad arguments"};
+        auto c = std::make_unique<bt_comm>();  // a failure below frees what was made so far
         c->rank = rank;
         c->world = world;
         c->device = device;
@@ -195,102 +176,74 @@ bt_comm* bt_comm_create(const uint8_t* id, int32_t rank, int32_t world, int32_t 
         ncclUniqueId uid;
         memcpy(&uid, id, sizeof uid);
         NCCLCHK(nc.CommInitRank(&c->comm, world, uid, rank));
-        HIPCHK(hipMalloc(&c->d_send, c->rec_bytes));
+        c->d_send.ensure(c->rec_bytes);
         for (int s = 0; s < BT_PIPE_SLOTS; ++s) {
-            HIPCHK(hipMalloc(&c->d_recv[s], c->rec_bytes * world));
-            HIPCHK(hipHostMalloc(&c->h_recv[s], c->rec_bytes * world));
-            HIPCHK(hipHostMalloc(&c->h_evals[s], sizeof(int64_t)));
-            HIPCHK(hipEventCreateWithFlags(&c->done[s], hipEventDisableTiming));
+            c->d_recv[s].ensure(c->rec_bytes * world);
+            c->h_recv[s].ensure(c->rec_bytes * world);
+            c->h_evals[s].ensure(1);
+            c->done[s].ensure(hipEventDisableTiming);
         }
-        return c;
-    } catch (const CommFail& f) {
-        release(c);
-        set_last_error(f.msg);
-        if (err && errlen) snprintf(err, errlen, "%s", f.msg.c_str());
-        return nullptr;
-    } catch (...) {
-        release(c);
-        set_last_error("unknown exception");
-        if (err && errlen) snprintf(err, errlen, "unknown exception");
-        return nullptr;
-    }
+        return c.release();
+    })
 }
 
-void bt_comm_destroy(bt_comm* c) { release(c); }
+void bt_comm_destroy(bt_comm* c) { delete c; }
 
 int32_t bt_exchange_async(bt_comm* c, bt_engine* e, int32_t slot) {
-    try {
-        if (!c || !e || slot < 0 || slot >= BT_PIPE_SLOTS) throw CommFail{"bad arguments"};
+    ABI_GUARD(-1, {
+        if (!c || !e || slot < 0 || slot >= BT_PIPE_SLOTS) throw HipFail{"bad arguments"};
         ExchangeView v{};
         std::string why;
-        if (!engine_exchange_view(e, v, why)) throw CommFail{why};
-        if (v.device != c->device) throw CommFail{"engine and communicator are on different devices"};
-        if (v.topk < c->k) throw CommFail{"engine topk is smaller than the communicator's k"};
+        if (!engine_exchange_view(e, v, why)) throw HipFail{why};
+        if (v.device != c->device) throw HipFail{"engine and communicator are on different devices"};
+        if (v.topk < c->k) throw HipFail{"engine topk is smaller than the communicator's k"};
         HIPCHK(hipSetDevice(c->device));
         // the slot's previous read-back must be consumed before its pinned buffers are reused
         if (c->armed[slot]) HIPCHK(hipEventSynchronize(c->done[slot]));
         const size_t recs = ((size_t)c->k + 1) * sizeof(bt_topk_rec);
-        unsigned char* cnt = c->d_send + recs;
-        *c->h_evals[slot] = v.bar_evals;
+        unsigned char* cnt = c->d_send.p + recs;
+        *c->h_evals[slot].p = v.bar_evals;
         // header + the first k records of the run's top-k, its trade counter, its bar-evals
-        HIPCHK(hipMemcpyAsync(c->d_send, v.d_top, recs, hipMemcpyDeviceToDevice, v.tstream));
-        HIPCHK(hipMemcpyAsync(cnt, c->h_evals[slot], sizeof(int64_t), hipMemcpyHostToDevice, v.tstream));
+        HIPCHK(hipMemcpyAsync(c->d_send.p, v.d_top, recs, hipMemcpyDeviceToDevice, v.tstream));
+        HIPCHK(hipMemcpyAsync(cnt, c->h_evals[slot].p, sizeof(int64_t), hipMemcpyHostToDevice, v.tstream));
         HIPCHK(hipMemcpyAsync(cnt + sizeof(int64_t), v.d_ntr, sizeof(int64_t), hipMemcpyDeviceToDevice,
                               v.tstream));
         engine_exchange_enqueued(e);
-        NCCLCHK(rccl().AllGather(c->d_send, c->d_recv[slot], c->rec_bytes, ncclChar, c->comm,
+        NCCLCHK(rccl().AllGather(c->d_send.p, c->d_recv[slot].p, c->rec_bytes, ncclChar, c->comm,
                                  v.tstream));
-        HIPCHK(hipMemcpyAsync(c->h_recv[slot], c->d_recv[slot], c->rec_bytes * c->world,
+        HIPCHK(hipMemcpyAsync(c->h_recv[slot].p, c->d_recv[slot].p, c->rec_bytes * c->world,
                               hipMemcpyDeviceToHost, v.tstream));
         HIPCHK(hipEventRecord(c->done[slot], v.tstream));
         c->armed[slot] = true;
         return 0;
-    } catch (const CommFail& f) {
-        set_last_error(f.msg);
-        return -1;
-    } catch (...) {
-        set_last_error("unknown exception");
-        return -1;
-    }
+    })
 }
 
 int32_t bt_exchange_wait(bt_comm* c, int32_t slot, bt_topk_rec* out, int32_t k,
                          int64_t* counters) {
-    try {
-        if (!c || slot < 0 || slot >= BT_PIPE_SLOTS || !out || k < 1) throw CommFail{"bad arguments"};
-        if (!c->armed[slot]) throw CommFail{"no exchange pending on this slot"};
+    ABI_GUARD(-1, {
+        if (!c || slot < 0 || slot >= BT_PIPE_SLOTS || !out || k < 1) throw HipFail{"bad arguments"};
+        if (!c->armed[slot]) throw HipFail{"no exchange pending on this slot"};
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipEventSynchronize(c->done[slot]));
         c->armed[slot] = false;
-        return merge_block(c->h_recv[slot], c->world, c->k, out, k, counters);
-    } catch (const CommFail& f) {
-        set_last_error(f.msg);
-        return -1;
-    } catch (...) {
-        set_last_error("unknown exception");
-        return -1;
-    }
+        return merge_block(c->h_recv[slot].p, c->world, c->k, out, k, counters);
+    })
 }
 
 int64_t bt_exchange_message_bytes(int32_t k) { return k < 1 ? -1 : (int64_t)message_bytes(k); }
 
 int32_t bt_exchange_merge(const uint8_t* block, size_t block_bytes, int32_t world, int32_t k_msg,
                           bt_topk_rec* out, int32_t k, int64_t* counters) {
-    try {
-        if (!block || world < 1 || k_msg < 1 || !out || k < 1) throw CommFail{"bad arguments"};
+    ABI_GUARD(-1, {
+        if (!block || world < 1 || k_msg < 1 || !out || k < 1) throw HipFail{"bad arguments"};
         // a short or mismatched block (a truncated gather, a rank that sent another k) is
         // rejected, never read past its end
         if (block_bytes != (size_t)world * message_bytes(k_msg))
-            throw CommFail{"block holds " + std::to_string(block_bytes) + " bytes, not world x " +
+            throw HipFail{"block holds " + std::to_string(block_bytes) + " bytes, not world x " +
                            std::to_string(message_bytes(k_msg))};
         return merge_block(block, world, k_msg, out, k, counters);
-    } catch (const CommFail& f) {
-        set_last_error(f.msg);
-        return -1;
-    } catch (...) {
-        set_last_error("unknown exception");
-        return -1;
-    }
+    })
 }
 
 }  // extern "C"

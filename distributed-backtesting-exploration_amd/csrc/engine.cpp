@@ -1,73 +1,34 @@
 // engine.cpp — the C ABI of include/bt.h: engine lifecycle, HBM-resident datasets, the
 // JobsReply batch entry point (drop-in for process_incoming_job,
-// /root/reference/src/worker/process.rs:13-29) and result serialisation.
+// /root/reference/src/worker/process.rs:13-29); its host half, ingest and result strings, is batch.cpp.
 //
 // Nothing here computes a backtest on the CPU: every result comes from the HIP kernels in
-// k_*.hip. The host parses CSV bytes (ingest), moves bars to HBM, launches, and formats
-// CompleteRequest.data strings (/root/reference/proto/backtesting.proto:29-32).
+// k_*.hip. The host moves bars to HBM, launches and reads back; the HIP objects it holds are the
+// self-freeing types of hip_owned.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <charconv>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
+#include <memory>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
+#include "batch.h"
 #include "csv.h"
+#include "hip_owned.h"
 #include "internal.h"
 #include "plan.h"
 #include "surface.h"
 
 using namespace bt;
 
-namespace {
+static thread_local std::string g_err;
 
-thread_local std::string g_err;
-
-void set_err(const std::string& s) { g_err = s; }
-
-struct HipFail {
-    std::string msg;
-};
-
-#define HIPCHK(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess)                                                                  \
-            throw HipFail{std::string(#x) + ": " + hipGetErrorString(e_)};                     \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    void ensure(size_t want) {
-        if (want <= n && p) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        if (want == 0) return;
-        HIPCHK(hipMalloc(&p, want * sizeof(T)));
-        n = want;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-}  // namespace
-
-void bt::set_last_error(const std::string& s) { set_err(s); }
+void bt::set_last_error(const std::string& s) { g_err = s; }
 
 constexpr int64_t kNtrRing = 64;  // per-run trade counter slots (bt_engine::d_ntr_ring)
 
@@ -76,8 +37,18 @@ struct bt_engine {
     std::vector<int32_t> ax[4];  // owned copies of the grid axes
     Grid grid{};
     int32_t P = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    // the engine stream (its own, or bt_config.stream borrowed) and the top-k chain stream (the
+    // chain of run i overlaps the kernel of run i+1). Declared before every buffer and event:
+    // members go in reverse order, so the streams outlive what was enqueued on them
+    Stream tstream, stream;
+    // What is still enqueued finishes before the members free what it uses. The engine stream is
+    // the first HIP object an engine makes: without it there is nothing to wait for.
+    ~bt_engine() {
+        if (!stream) return;
+        (void)hipSetDevice(cfg.device);
+        (void)hipStreamSynchronize(stream);
+        if (tstream) (void)hipStreamSynchronize(tstream);
+    }
     DevBuf<int32_t> d_axes[4];
     DevBuf<int32_t> d_kwin;      // SMA: Grid::kwin, Grid::krecip
     DevBuf<double> d_krecip;
@@ -109,33 +80,29 @@ struct bt_engine {
     DevBuf<double> d_segema;
     DevBuf<unsigned long long> d_refixed;
     DevBuf<unsigned long long> d_dbg;
-    // top-k chain stream: the chain of run i overlaps the kernel of run i+1
-    hipStream_t tstream = nullptr;
-    hipEvent_t ev_kdone = nullptr;          // kernel of the last run finished (main stream)
-    hipEvent_t ev_tdone[2] = {nullptr, nullptr};  // readers of buffer b finished (tstream)
+    Event ev_kdone;      // kernel of the last run finished (main stream)
+    Event ev_tdone[2];   // readers of buffer b finished (tstream)
     bool tdone_armed[2] = {false, false};
     // top-k work
     DevBuf<unsigned int> d_hist, d_counts;
     DevBuf<unsigned long long> d_state, d_above, d_cand;
     DevBuf<bt_topk_rec> d_top;
-    bt_topk_rec* h_top = nullptr;     // pinned host copy of d_top
+    PinnedBuf<bt_topk_rec> h_top;     // pinned host copy of d_top
     // pipelined read-back slots: header + kTopkMax records + one record holding the trade count
-    bt_topk_rec* h_slot[BT_PIPE_SLOTS] = {};
-    hipEvent_t slot_ev[BT_PIPE_SLOTS] = {};
+    PinnedBuf<bt_topk_rec> h_slot[BT_PIPE_SLOTS];
+    Event slot_ev[BT_PIPE_SLOTS];
     bool slot_armed[BT_PIPE_SLOTS] = {};
     bool topk_ready = false;          // top-k buffers allocated and their state initialised
     bool ran = false;
     // timing of the dominant kernel
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending, ev_pool;
+    std::vector<std::pair<Event, Event>> ev_pending, ev_pool;
     double kernel_ms = 0.0;
     int64_t launches = 0;
     // bt_run_batch: pinned host staging of the columns in device row layout (c, h, l), the
     // batch's summaries read back in one copy, phase events and the last batch's profile
-    int32_t* h_stage[3] = {nullptr, nullptr, nullptr};
-    size_t stage_rows[3] = {0, 0, 0};
-    bt_summary* h_sum = nullptr;
-    size_t h_sum_n = 0;
-    hipEvent_t ev_batch[4] = {nullptr, nullptr, nullptr, nullptr};
+    PinnedBuf<int32_t> h_stage[3];
+    PinnedBuf<bt_summary> h_sum;
+    Event ev_batch[4];
     bt_batch_profile prof{};
     int64_t n_errors = 0;
     // bt_replay: device staging of one chunk of requests (descriptors, summaries, trades, curves),
@@ -145,8 +112,7 @@ struct bt_engine {
     // one reduction, and the matrix and ids bt_surface_of stages
     int32_t surface_chunks = 0;
     DevBuf<uint8_t> d_surface, d_surface_in;
-    uint8_t* h_surface = nullptr;  // pinned: the results of one reduction
-    size_t h_surface_n = 0;
+    PinnedBuf<uint8_t> h_surface;  // the results of one reduction
 };
 
 namespace {
@@ -203,7 +169,7 @@ void upload_grid(bt_engine* e) {
     }
 }
 
-int64_t align_rows(int64_t bars) { return (bars + kRowAlign - 1) / kRowAlign * kRowAlign; }
+static_assert(kStageAlign == kRowAlign, "batch.h lays staging rows out as the device columns");
 
 void sync_all(bt_engine* e);
 
@@ -245,16 +211,6 @@ void layout(bt_engine* e, int32_t n_sym, const int32_t* bars, const int64_t* ids
     set_dataset(e, std::move(syms), off);
 }
 
-template <class T>
-void ensure_pinned(T*& p, size_t& have, size_t want) {
-    if (want <= have && p) return;
-    if (p) HIPCHK(hipHostFree(p));
-    p = nullptr;
-    have = 0;
-    HIPCHK(hipHostMalloc(&p, std::max<size_t>(want, 1) * sizeof(T)));
-    have = std::max<size_t>(want, 1);
-}
-
 TopkWork topk_work(bt_engine* e) {
     return TopkWork{e->d_hist.p, e->d_state.p, e->d_counts.p, e->d_above.p, e->d_cand.p,
                     kTopkCap, e->d_top.p + 1, reinterpret_cast<int32_t*>(e->d_top.p)};
@@ -283,7 +239,7 @@ void ensure_outputs(bt_engine* e) {
         e->d_above.ensure(kTopkCap);
         e->d_cand.ensure(kTopkCap);
         e->d_top.ensure(kTopkMax + 1);  // [0] = header (record count), then the records
-        if (!e->h_top) HIPCHK(hipHostMalloc(&e->h_top, (kTopkMax + 1) * sizeof(bt_topk_rec)));
+        e->h_top.ensure(kTopkMax + 1);
         HIPCHK(launch_topk_init(topk_work(e), e->stream));
         e->topk_ready = true;
     }
@@ -321,15 +277,14 @@ void run_impl(bt_engine* e) {
         out.dbg = e->d_dbg.p;
     }
     const bool timing = (e->cfg.flags & BT_FLAG_TIMING) != 0;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
+    std::pair<Event, Event> ev;  // ours until it reaches ev_pending: a throw before that destroys it
     if (timing) {
         if (!e->ev_pool.empty()) {
-            ev = e->ev_pool.back();
+            ev = std::move(e->ev_pool.back());
             e->ev_pool.pop_back();
-        } else {
-            HIPCHK(hipEventCreate(&ev.first));
-            HIPCHK(hipEventCreate(&ev.second));
         }
+        ev.first.ensure(0);
+        ev.second.ensure(0);
         HIPCHK(hipEventRecord(ev.first, e->stream));
     }
     const LaunchPlan pl = plan_launch(e->grid, e->ax[0].data(),
@@ -362,15 +317,17 @@ void run_impl(bt_engine* e) {
             break;
     }
     HIPCHK(err);
+    hipEvent_t kdone = e->ev_kdone;
     if (timing) {
         HIPCHK(hipEventRecord(ev.second, e->stream));
-        e->ev_pending.push_back(ev);
+        kdone = ev.second;
+        e->ev_pending.push_back(std::move(ev));
     }
     if (e->cfg.topk > 0) {
         // the chain waits for the kernel: on the timing end event when there is one (one
         // marker less between two runs' kernels)
-        if (!timing) HIPCHK(hipEventRecord(e->ev_kdone, e->stream));
-        HIPCHK(hipStreamWaitEvent(e->tstream, timing ? ev.second : e->ev_kdone, 0));
+        if (!timing) HIPCHK(hipEventRecord(kdone, e->stream));
+        HIPCHK(hipStreamWaitEvent(e->tstream, kdone, 0));
         HIPCHK(launch_topk(e->d_key[b].p, e->d_sum[b].p, e->d_syms.p, (int64_t)S * e->P, e->P,
                            e->cfg.topk, topk_work(e), e->tstream, pl.topk_lds_free));
         HIPCHK(hipEventRecord(e->ev_tdone[b], e->tstream));
@@ -498,11 +455,11 @@ void surface_launch(bt_engine* e, const bt_summary* d_sum, const int32_t* d_ids,
     const size_t n_agg = (size_t)P * sizeof(bt_param_agg), n_best = (size_t)S * sizeof(bt_topk_rec);
     const size_t lo = agg ? o_agg : o_best, hi = best && S > 0 ? o_best + n_best : o_agg + n_agg;
     if (hi <= lo) return;  // best alone of a matrix without rows
-    ensure_pinned(e->h_surface, e->h_surface_n, hi - lo);
-    HIPCHK(hipMemcpyAsync(e->h_surface, base + lo, hi - lo, hipMemcpyDeviceToHost, e->stream));
+    e->h_surface.ensure(hi - lo);
+    HIPCHK(hipMemcpyAsync(e->h_surface.p, base + lo, hi - lo, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (agg) memcpy(agg, e->h_surface + (o_agg - lo), n_agg);
-    if (best && S > 0) memcpy(best, e->h_surface + (o_best - lo), n_best);
+    if (agg) memcpy(agg, e->h_surface.p + (o_agg - lo), n_agg);
+    if (best && S > 0) memcpy(best, e->h_surface.p + (o_best - lo), n_best);
 }
 
 int32_t surface_impl(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
@@ -551,7 +508,7 @@ void drain_timing(bt_engine* e) {
         HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
         e->kernel_ms += ms;
         e->launches += 1;
-        e->ev_pool.push_back(ev);
+        e->ev_pool.push_back(std::move(ev));
     }
     e->ev_pending.clear();
 }
@@ -561,221 +518,46 @@ std::vector<bt_topk_rec> read_topk_impl(bt_engine* e, int32_t k) {
     if (!e->ran || e->cfg.topk <= 0) throw HipFail{"top-k not computed (topk == 0 or no run)"};
     // header + the configured k records in one copy into pinned memory
     const size_t nrec = (size_t)e->cfg.topk + 1;
-    HIPCHK(hipMemcpyAsync(e->h_top, e->d_top.p, nrec * sizeof(bt_topk_rec), hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(e->h_top.p, e->d_top.p, nrec * sizeof(bt_topk_rec), hipMemcpyDeviceToHost,
                           e->tstream));
     sync_all(e);
     int32_t n = 0;
-    memcpy(&n, e->h_top, sizeof n);
+    memcpy(&n, e->h_top.p, sizeof n);
     // the device selection is complete whatever the ties (k_topk.hip topk_finish_ties)
     if (n < 0 || n > e->cfg.topk) throw HipFail{"device top-k returned a bad record count"};
-    std::vector<bt_topk_rec> res(e->h_top + 1, e->h_top + 1 + n);
+    std::vector<bt_topk_rec> res(e->h_top.p + 1, e->h_top.p + 1 + n);
     if ((int32_t)res.size() > k) res.resize(k);
     return res;
 }
 
-// One CompleteRequest.data line (spec §6). std::to_chars gives printf's "%.17g" (general
-// format, precision 17) and plain decimal integers without the locale and format-string work of
-// snprintf; tests/test_abi_cpu.py checks the bytes against Python's "%.17g" / "%016x".
-char* put_lit(char* q, const char* s) {
-    while (*s) *q++ = *s++;
-    return q;
-}
-
-char* fmt_line(char* q, int32_t p, const bt_summary& x) {
-    static const char kHex[] = "0123456789abcdef";
-    q = put_lit(q, "{\"param\":");
-    q = std::to_chars(q, q + 16, p).ptr;
-    q = put_lit(q, ",\"n\":");
-    q = std::to_chars(q, q + 16, x.n_trades).ptr;
-    q = put_lit(q, ",\"pnl\":");
-    q = std::to_chars(q, q + 24, (long long)x.pnl).ptr;
-    q = put_lit(q, ",\"mdd\":");
-    q = std::to_chars(q, q + 24, (long long)x.mdd).ptr;
-    q = put_lit(q, ",\"exp\":");
-    q = std::to_chars(q, q + 24, (long long)x.exposure).ptr;
-    q = put_lit(q, ",\"sharpe\":\"");
-    q = std::to_chars(q, q + 32, x.sharpe, std::chars_format::general, 17).ptr;
-    q = put_lit(q, "\",\"h\":\"");
-    for (int i = 15; i >= 0; --i) *q++ = kHex[(x.hash >> (4 * i)) & 15];
-    return put_lit(q, "\"}\n");
-}
-
-constexpr size_t kLineMax = 192;  // longest line: 10 + 11 + 20 x 3 + 24 + 16 + fixed text < 192
-
-size_t fmt_job_into(const bt_summary* r, int32_t P, char* out) {
-    char* q = out;
-    for (int32_t p = 0; p < P; ++p) q = fmt_line(q, p, r[p]);
-    return (size_t)(q - out);
-}
-
-std::string json_escape(const std::string& in) {
-    std::string o;
-    for (char ch : in) {
-        if (ch == '"' || ch == '\\') {
-            o.push_back('\\');
-            o.push_back(ch);
-        } else if ((unsigned char)ch < 0x20) {
-            o.push_back(' ');
-        } else {
-            o.push_back(ch);
-        }
-    }
-    return o;
-}
-
-char* dup_string(const std::string& s) {
-    char* p = (char*)malloc(s.size() + 1);
-    if (!p) throw std::bad_alloc();
-    memcpy(p, s.data(), s.size());
-    p[s.size()] = 0;
-    return p;
-}
-
-
-// Host threads of the batch ingest: host_threads, else the machine's, at most 16 (the worker's
-// share of a GPU box; /root/reference/src/worker/handlers.rs:35 reports num_cpus/2 as cores).
-int host_threads(const bt_engine* e, size_t n) {
-    int nt = e->cfg.host_threads > 0
-                 ? e->cfg.host_threads
-                 : (int)std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
-    return (int)std::min<size_t>((size_t)nt, std::max<size_t>(1, n));
-}
-
-// f(i) for i in [0, n) on nt threads (f must not throw).
-template <class F>
-void parallel_for(int nt, size_t n, const F& f) {
-    std::atomic<size_t> next{0};
-    auto work = [&]() {
-        for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
-    };
-    if (nt <= 1 || n <= 1) {
-        work();
-        return;
-    }
-    std::vector<std::thread> th;
-    th.reserve((size_t)nt);
-    for (int i = 0; i < nt; ++i) th.emplace_back(work);
-    for (auto& t : th) t.join();
-}
-
-struct JobSlot {
-    bool ok = false, binary = false;
-    int32_t bars = 0;
-    int64_t row = 0;
-    size_t sym = 0;
-    Bars parsed;  // CSV jobs only (binary payloads decode straight into the staging rows)
-    std::string err;
-};
-
-double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
-}
-
-// The JobsReply as one GPU batch (drop-in for process_incoming_job's loop,
-// /root/reference/src/worker/process.rs:21-25):
-//   1. per job (host threads): binary payloads -> bar count from the header; CSV -> parsed;
-//   2. rows of the good jobs laid out 64-aligned in pinned host staging;
-//   3. per job (host threads): binary payloads validated and decoded straight into their rows
-//      in one pass (decode_binary_into), CSV bars copied in;
-//   4. one async H2D per column, the strategy kernel, one D2H of every summary, one wait;
-//   5. per job (host threads): the CompleteRequest.data string.
+// The device half of bt_run_batch (step 4 of batch.h's Batch): pinned staging for the host half
+// to fill, then one async H2D per column, the strategy kernel, one D2H of every summary, one wait.
 void run_batch_impl(bt_engine* e, size_t n, const bt_job_in* jobs, bt_job_out* outs) {
-    using clk = std::chrono::steady_clock;
-    const auto t_start = clk::now();
+    Batch bat(n, jobs, e->cfg.host_threads);
     activate(e);
     sync_all(e);  // staging and h_sum may still be in use by an earlier call
-    bt_batch_profile pr{};
-    pr.n_jobs = (int64_t)n;
-    const int nt = host_threads(e, n);
-    const bool hl = has_hl(e);
-    std::vector<JobSlot> js(n);
-    for (size_t i = 0; i < n; ++i) pr.payload_bytes += (int64_t)jobs[i].len;
-    parallel_for(nt, n, [&](size_t i) {
-        JobSlot& j = js[i];
-        try {
-            const uint8_t* buf = jobs[i].file;
-            const size_t len = jobs[i].len;
-            if (!buf && len) {
-                j.err = "null Job.File";
-            } else if (buf && is_binary_payload(buf, len)) {
-                j.binary = true;
-                j.ok = binary_header(buf, len, j.bars, j.err);
-            } else {
-                j.ok = parse_csv(buf, len, j.parsed, j.err);
-                j.bars = (int32_t)j.parsed.c.size();
-            }
-        } catch (...) {
-            j.ok = false;
-            j.err = "parse failure";
-        }
-    });
-    int64_t rows = 0;
-    for (size_t i = 0; i < n; ++i) {
-        JobSlot& j = js[i];
-        // what ingest touches: a CSV is parsed whole; a binary payload's header and its four price
-        // columns are validated, its volume column is never read
-        if (j.ok) pr.payload_bytes_read += j.binary ? (int64_t)binary_payload_size(j.bars, false)
-                                                    : (int64_t)jobs[i].len;
-        if (j.ok) {
-            j.row = rows;
-            rows += align_rows(j.bars);
-        }
-    }
-    const int ncol = hl ? 3 : 1;
-    for (int k = 0; k < ncol; ++k) ensure_pinned(e->h_stage[k], e->stage_rows[k], (size_t)std::max<int64_t>(rows, 1));
-    parallel_for(nt, n, [&](size_t i) {
-        JobSlot& j = js[i];
-        if (!j.ok) return;
-        try {
-            int32_t* c = e->h_stage[0] + j.row;
-            int32_t* h = hl ? e->h_stage[1] + j.row : nullptr;
-            int32_t* l = hl ? e->h_stage[2] + j.row : nullptr;
-            if (j.binary) {
-                j.ok = decode_binary_into(jobs[i].file, jobs[i].len, h, l, c, j.err);
-            } else {
-                memcpy(c, j.parsed.c.data(), (size_t)j.bars * 4);
-                if (hl) {
-                    memcpy(h, j.parsed.h.data(), (size_t)j.bars * 4);
-                    memcpy(l, j.parsed.l.data(), (size_t)j.bars * 4);
-                }
-                j.parsed = Bars();  // release early
-            }
-        } catch (...) {
-            j.ok = false;
-            j.err = "ingest failure";
-        }
-    });
-    // a job that failed in step 3 leaves its rows unreferenced
-    std::vector<SymDesc> syms;
-    e->n_errors = 0;
-    for (JobSlot& j : js) {
-        if (!j.ok) {
-            ++e->n_errors;
-            continue;
-        }
-        j.sym = syms.size();
-        syms.push_back(SymDesc{j.row, j.bars, (int32_t)syms.size()});
-        pr.bars += j.bars;
-    }
-    const auto t_staged = clk::now();
-    pr.host_ingest_ms = ms_between(t_start, t_staged);
-    pr.n_failed = e->n_errors;
-    const int32_t P = e->P;
-    const size_t nres = syms.size() * (size_t)P;
-    if (!syms.empty()) {
-        for (hipEvent_t& ev : e->ev_batch)
-            if (!ev) HIPCHK(hipEventCreate(&ev));
-        ensure_pinned(e->h_sum, e->h_sum_n, nres);
+    const int64_t rows = bat.parse();
+    const int ncol = has_hl(e) ? 3 : 1;
+    for (int k = 0; k < ncol; ++k) e->h_stage[k].ensure((size_t)rows);
+    bat.stage(e->h_stage[0].p, ncol == 3 ? e->h_stage[1].p : nullptr, ncol == 3 ? e->h_stage[2].p : nullptr);
+    bt_batch_profile& pr = bat.prof;
+    e->n_errors = pr.n_failed;
+    const size_t nres = bat.syms.size() * (size_t)e->P;
+    if (!bat.syms.empty()) {
+        std::vector<SymDesc> syms;
+        for (const StagedSym& s : bat.syms) syms.push_back(SymDesc{s.row, s.bars, (int32_t)syms.size()});
+        for (Event& ev : e->ev_batch) ev.ensure(0);
+        e->h_sum.ensure(nres);
         set_dataset(e, std::move(syms), rows);
         HIPCHK(hipEventRecord(e->ev_batch[0], e->stream));
         int32_t* dst[3] = {e->d_c.p, e->d_h.p, e->d_l.p};
         for (int k = 0; k < ncol; ++k)
-            HIPCHK(hipMemcpyAsync(dst[k], e->h_stage[k], (size_t)rows * 4, hipMemcpyHostToDevice,
+            HIPCHK(hipMemcpyAsync(dst[k], e->h_stage[k].p, (size_t)rows * 4, hipMemcpyHostToDevice,
                                   e->stream));
         HIPCHK(hipEventRecord(e->ev_batch[1], e->stream));
         run_impl(e);
         HIPCHK(hipEventRecord(e->ev_batch[2], e->stream));
-        HIPCHK(hipMemcpyAsync(e->h_sum, e->d_sum[e->cur].p, nres * sizeof(bt_summary),
+        HIPCHK(hipMemcpyAsync(e->h_sum.p, e->d_sum[e->cur].p, nres * sizeof(bt_summary),
                               hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipEventRecord(e->ev_batch[3], e->stream));
         sync_all(e);
@@ -787,30 +569,7 @@ void run_batch_impl(bt_engine* e, size_t n, const bt_job_in* jobs, bt_job_out* o
         HIPCHK(hipEventElapsedTime(&ms, e->ev_batch[2], e->ev_batch[3]));
         pr.readback_ms = ms;
     }
-    const auto t_dev = clk::now();
-    std::atomic<bool> alloc_fail{false};
-    parallel_for(nt, n, [&](size_t i) {
-        try {
-            const JobSlot& j = js[i];
-            if (j.ok) {
-                char* buf = (char*)malloc((size_t)P * kLineMax + 1);
-                if (!buf) throw std::bad_alloc();
-                const size_t len = fmt_job_into(e->h_sum + j.sym * (size_t)P, P, buf);
-                buf[len] = 0;
-                char* fit = (char*)realloc(buf, len + 1);
-                outs[i] = bt_job_out{fit ? fit : buf, len, 0, j.bars};
-            } else {
-                const std::string m = "{\"error\":\"" + json_escape(j.err) + "\"}\n";
-                outs[i] = bt_job_out{dup_string(m), m.size(), -1, 0};
-            }
-        } catch (...) {
-            alloc_fail = true;
-        }
-    });
-    if (alloc_fail) throw std::bad_alloc();
-    const auto t_end = clk::now();
-    pr.format_ms = ms_between(t_dev, t_end);
-    pr.total_ms = ms_between(t_start, t_end);
+    bat.format(e->h_sum.p, e->P, outs);
     e->prof = pr;
 }
 
@@ -839,149 +598,57 @@ void bt::engine_exchange_enqueued(bt_engine* e) {
     if (hipEventRecord(e->ev_tdone[e->cur], e->tstream) == hipSuccess) e->tdone_armed[e->cur] = true;
 }
 
-namespace {
-
-#define ABI_GUARD(fail, ...)                                   \
-    try {                                                      \
-        __VA_ARGS__                                            \
-    } catch (const HipFail& f) {                               \
-        set_err(f.msg);                                        \
-        return fail;                                           \
-    } catch (const std::exception& x) {                        \
-        set_err(std::string("exception: ") + x.what());        \
-        return fail;                                           \
-    } catch (...) {                                            \
-        set_err("unknown exception");                          \
-        return fail;                                           \
-    }
-
-}  // namespace
-
 extern "C" {
 
 int32_t bt_abi_version(void) { return BT_ABI_VERSION; }
 
 const char* bt_last_error(void) { return g_err.c_str(); }
 
+static bt_engine* create_impl(const bt_config* cfg) {
+    if (cfg == nullptr) throw HipFail{"null config"};
+    auto e = std::make_unique<bt_engine>();  // a failure below frees what was made so far
+    e->cfg = *cfg;
+    const std::string m = validate_and_copy(e.get(), *cfg);
+    if (!m.empty()) throw HipFail{m};
+    e->cfg.fast = e->cfg.slow = e->cfg.span = e->cfg.ols = nullptr;
+    e->cfg.bwin = e->cfg.k_num = e->cfg.sl_bps = e->cfg.tp_bps = nullptr;
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (cfg->device < 0 || cfg->device >= ndev)
+        throw HipFail{"HIP device " + std::to_string(cfg->device) + " not present (" +
+                      std::to_string(ndev) + " visible)"};
+    activate(e.get());
+    if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess ||
+        e->cus <= 0)
+        e->cus = kCusFallback;
+    if (cfg->stream)
+        e->stream.borrow((hipStream_t)cfg->stream);
+    else
+        e->stream.create();
+    e->tstream.create();
+    e->ev_kdone.ensure(hipEventDisableTiming);
+    for (Event& ev : e->ev_tdone) ev.ensure(hipEventDisableTiming);
+    upload_grid(e.get());
+#ifdef BT_PROFILING
+    if (const char* ab = getenv("BT_ABLATE")) e->grid.ablate = atoi(ab);  // profiling build only
+#endif
+    return e.release();
+}
+
 bt_engine* bt_engine_create(const bt_config* cfg, char* err, size_t errlen) {
-    auto fail = [&](const std::string& m) -> bt_engine* {
-        set_err(m);
-        if (err && errlen) snprintf(err, errlen, "%s", m.c_str());
+    auto failed = [&]() -> bt_engine* {  // bt_last_error() into the caller's buffer too
+        if (err && errlen) snprintf(err, errlen, "%s", g_err.c_str());
         return nullptr;
     };
-    if (cfg == nullptr) return fail("null config");
-    bt_engine* e = nullptr;
-    try {
-        e = new bt_engine();
-        e->cfg = *cfg;
-        std::string m = validate_and_copy(e, *cfg);
-        if (!m.empty()) {
-            delete e;
-            return fail(m);
-        }
-        e->cfg.fast = e->cfg.slow = e->cfg.span = e->cfg.ols = nullptr;
-        e->cfg.bwin = e->cfg.k_num = e->cfg.sl_bps = e->cfg.tp_bps = nullptr;
-        int ndev = 0;
-        HIPCHK(hipGetDeviceCount(&ndev));
-        if (cfg->device < 0 || cfg->device >= ndev)
-            throw HipFail{"HIP device " + std::to_string(cfg->device) + " not present (" +
-                          std::to_string(ndev) + " visible)"};
-        activate(e);
-        if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess ||
-            e->cus <= 0)
-            e->cus = kCusFallback;
-        if (cfg->stream) {
-            e->stream = (hipStream_t)cfg->stream;
-        } else {
-            HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-            e->own_stream = true;
-        }
-        HIPCHK(hipStreamCreateWithFlags(&e->tstream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&e->ev_kdone, hipEventDisableTiming));
-        for (int b = 0; b < 2; ++b) HIPCHK(hipEventCreateWithFlags(&e->ev_tdone[b], hipEventDisableTiming));
-        upload_grid(e);
-#ifdef BT_PROFILING
-        if (const char* ab = getenv("BT_ABLATE")) e->grid.ablate = atoi(ab);  // profiling build only
-#endif
-        return e;
-    } catch (const HipFail& f) {
-        delete e;
-        return fail(f.msg);
-    } catch (const std::exception& x) {
-        delete e;
-        return fail(std::string("exception: ") + x.what());
-    }
+    ABI_GUARD(failed(), { return create_impl(cfg); })
 }
 
 void bt_engine_destroy(bt_engine* e) {
     if (!e) return;
     try {
-        (void)hipSetDevice(e->cfg.device);
-        if (e->stream) (void)hipStreamSynchronize(e->stream);
-        if (e->tstream) (void)hipStreamSynchronize(e->tstream);
-        for (auto& ev : e->ev_pending) {
-            (void)hipEventDestroy(ev.first);
-            (void)hipEventDestroy(ev.second);
-        }
-        for (auto& ev : e->ev_pool) {
-            (void)hipEventDestroy(ev.first);
-            (void)hipEventDestroy(ev.second);
-        }
-        for (auto& b : e->d_axes) b.release();
-        e->d_kwin.release();
-        e->d_krecip.release();
-        e->d_syms.release();
-        e->d_c.release();
-        e->d_h.release();
-        e->d_l.release();
-        for (int b = 0; b < 2; ++b) {
-            e->d_sum[b].release();
-            e->d_key[b].release();
-            if (e->ev_tdone[b]) (void)hipEventDestroy(e->ev_tdone[b]);
-            e->ev_tdone[b] = nullptr;
-            e->tdone_armed[b] = false;
-        }
-        if (e->ev_kdone) (void)hipEventDestroy(e->ev_kdone);
-        e->ev_kdone = nullptr;
-        e->d_ntr_ring.release();
-        e->d_sums.release();
-        e->d_trades.release();
-        e->d_seg.release();
-        e->d_segema.release();
-        e->d_refixed.release();
-        e->d_dbg.release();
-        e->d_replay.release();
-        e->d_surface.release();
-        e->d_surface_in.release();
-        if (e->h_surface) (void)hipHostFree(e->h_surface);
-        e->h_surface = nullptr;
-        e->d_hist.release();
-        e->d_counts.release();
-        e->d_state.release();
-        e->d_above.release();
-        e->d_cand.release();
-        e->d_top.release();
-        if (e->h_top) (void)hipHostFree(e->h_top);
-        e->h_top = nullptr;
-        for (int i = 0; i < BT_PIPE_SLOTS; ++i) {
-            if (e->h_slot[i]) (void)hipHostFree(e->h_slot[i]);
-            if (e->slot_ev[i]) (void)hipEventDestroy(e->slot_ev[i]);
-            e->h_slot[i] = nullptr;
-            e->slot_ev[i] = nullptr;
-            e->slot_armed[i] = false;
-        }
-        e->topk_ready = false;
-        for (int i = 0; i < 3; ++i)
-            if (e->h_stage[i]) (void)hipHostFree(e->h_stage[i]);
-        if (e->h_sum) (void)hipHostFree(e->h_sum);
-        for (hipEvent_t& ev : e->ev_batch)
-            if (ev) (void)hipEventDestroy(ev);
-        if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
-        if (e->tstream) (void)hipStreamDestroy(e->tstream);
-        e->tstream = nullptr;
+        delete e;
     } catch (...) {
     }
-    delete e;
 }
 
 int32_t bt_num_params(const bt_engine* e) { return e ? e->P : -1; }
@@ -1048,10 +715,10 @@ int32_t bt_load_ohlc(bt_engine* e, int32_t n_sym, const int64_t* sym_ids, const 
         int32_t* dst[3] = {e->d_c.p, e->d_h.p, e->d_l.p};
         if (e->rows > 0) {
             for (int k = 0; k < ncol; ++k) {
-                ensure_pinned(e->h_stage[k], e->stage_rows[k], (size_t)e->rows);
+                e->h_stage[k].ensure((size_t)e->rows);
                 for (int32_t s = 0; s < n_sym; ++s)
-                    memcpy(e->h_stage[k] + e->syms[s].off, src[k] + row_off[s], (size_t)bars[s] * 4);
-                HIPCHK(hipMemcpyAsync(dst[k], e->h_stage[k], (size_t)e->rows * 4,
+                    memcpy(e->h_stage[k].p + e->syms[s].off, src[k] + row_off[s], (size_t)bars[s] * 4);
+                HIPCHK(hipMemcpyAsync(dst[k], e->h_stage[k].p, (size_t)e->rows * 4,
                                       hipMemcpyHostToDevice, e->stream));
             }
             sync_all(e);
@@ -1126,10 +793,9 @@ int32_t bt_topk_fetch_async(bt_engine* e, int32_t slot) {
         if (!e || slot < 0 || slot >= BT_PIPE_SLOTS) throw HipFail{"bad arguments"};
         if (!e->ran || e->cfg.topk <= 0) throw HipFail{"top-k not computed (topk == 0 or no run)"};
         activate(e);
-        if (!e->h_slot[slot])
-            HIPCHK(hipHostMalloc(&e->h_slot[slot], (kTopkMax + 2) * sizeof(bt_topk_rec)));
-        if (!e->slot_ev[slot]) HIPCHK(hipEventCreateWithFlags(&e->slot_ev[slot], hipEventDisableTiming));
-        bt_topk_rec* h = e->h_slot[slot];
+        e->h_slot[slot].ensure(kTopkMax + 2);
+        e->slot_ev[slot].ensure(hipEventDisableTiming);
+        bt_topk_rec* h = e->h_slot[slot].p;
         // behind the run's top-k chain on tstream; the trade counter of the run's buffer is
         // complete too (the chain waited for the kernel)
         HIPCHK(hipMemcpyAsync(h, e->d_top.p, ((size_t)e->cfg.topk + 1) * sizeof(bt_topk_rec),
@@ -1150,7 +816,7 @@ int32_t bt_topk_fetch_wait(bt_engine* e, int32_t slot, bt_topk_rec* out, int32_t
         if (!e->slot_armed[slot]) throw HipFail{"no fetch pending on this slot"};
         activate(e);
         HIPCHK(hipEventSynchronize(e->slot_ev[slot]));
-        const bt_topk_rec* h = e->h_slot[slot];
+        const bt_topk_rec* h = e->h_slot[slot].p;
         int32_t n = 0;
         memcpy(&n, h, sizeof n);
         if (n < 0 || n > e->cfg.topk) throw HipFail{"device top-k returned a bad record count"};
@@ -1286,12 +952,7 @@ int64_t bt_format_summaries(const bt_summary* r, int32_t P, char* out, size_t ca
 }
 
 void bt_job_out_free(bt_job_out* outs, size_t n) {
-    if (!outs) return;
-    for (size_t i = 0; i < n; ++i) {
-        free(outs[i].data);
-        outs[i].data = nullptr;
-        outs[i].len = 0;
-    }
+    if (outs) free_job_outs(outs, n);
 }
 
 int32_t bt_merge_topk(const bt_topk_rec* in, size_t n, int32_t k, bt_topk_rec* out) {
@@ -1345,7 +1006,7 @@ int32_t bt_parse_job(const uint8_t* buf, size_t len, int32_t cap, int32_t* h, in
         std::string m;
         if (!parse_job(buf, len, b, m)) {
             if (err && errlen) snprintf(err, errlen, "%s", m.c_str());
-            set_err(m);
+            set_last_error(m);
             return -1;
         }
         if ((int64_t)b.c.size() > cap) throw HipFail{"cap too small"};

@@ -1,8 +1,10 @@
 """The host ingest (csv.cpp, payload.cpp: every Job.File byte the worker receives goes through
-it) under AddressSanitizer and UBSan, host code only: built with g++ next to a small driver
+it) and the host half of bt_run_batch (batch.cpp: row layout, staging from 4 threads, the result
+strings) under AddressSanitizer and UBSan, host code only: built with g++ next to a small driver
 (tests/asan/ingest_driver.cpp) and run over generated CSV / DBXCOL1 files, valid and corrupted
 (truncations, byte edits, huge bar counts, empty files). Any out-of-bounds access, overflow or
-undefined behaviour aborts the driver."""
+undefined behaviour aborts the driver, and so does a staged row or a string that differs from what
+the driver expects."""
 import os
 import shutil
 import subprocess
@@ -53,7 +55,8 @@ def test_ingest_under_asan_and_ubsan(tmp_path):
                         "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
                         "-I", CSRC, "-I", os.path.join(ROOT, "include"),
                         os.path.join(ROOT, "tests", "asan", "ingest_driver.cpp"),
-                        os.path.join(CSRC, "csv.cpp"), os.path.join(CSRC, "payload.cpp"), "-o", exe],
+                        os.path.join(CSRC, "csv.cpp"), os.path.join(CSRC, "payload.cpp"),
+                        os.path.join(CSRC, "batch.cpp"), "-pthread", "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     files = _corpus(str(tmp_path))
