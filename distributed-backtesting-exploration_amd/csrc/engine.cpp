@@ -23,6 +23,7 @@
 #include "internal.h"
 #include "plan.h"
 #include "surface.h"
+#include "walkfwd.h"
 
 using namespace bt;
 
@@ -113,6 +114,10 @@ struct bt_engine {
     int32_t surface_chunks = 0;
     DevBuf<uint8_t> d_surface, d_surface_in;
     PinnedBuf<uint8_t> h_surface;  // the results of one reduction
+    // bt_walk_forward: the staging budget asked for (0 = kWalkfwdBudget) and the device staging
+    // of one chunk of rows (bounds, fold records, steps), never more than the budget
+    int64_t walkfwd_budget = 0;
+    DevBuf<uint8_t> d_walkfwd;
 };
 
 namespace {
@@ -501,6 +506,66 @@ int32_t surface_of_impl(bt_engine* e, int32_t S, int32_t P, const bt_summary* su
     return 0;
 }
 
+// ---- bt_walk_forward: every lane's folds and the out-of-sample picks (k_walkfwd.hip)
+// The rows go through the device in the chunks of the WalkfwdPlan: per chunk the records are
+// zeroed, walked, selected from and copied out; the totals are folded on the host (walkfwd.cpp).
+int32_t walk_forward_impl(bt_engine* e, int32_t K, const int32_t* bounds, int32_t train, bt_fold* folds,
+                          bt_wf_step* steps, bt_fold* total) {
+    auto refuse = [](const std::string& m) { throw HipFail{"bt_walk_forward: " + m}; };
+    if (!e) refuse("null engine");
+    if (e->syms.empty()) refuse("no dataset loaded");
+    if (K >= 1 && !bounds) refuse("bounds are required");
+    const int32_t S = (int32_t)e->syms.size(), P = e->P;
+    const std::string why = walkfwd_refusal(K, bounds, train, folds != nullptr, steps != nullptr,
+                                            total != nullptr, S, P);
+    if (!why.empty()) refuse(why);
+    const WalkfwdPlan pl = plan_walkfwd(S, P, K, e->max_bars, e->cus, e->walkfwd_budget);
+    if (pl.rows_per_chunk < 1)
+        refuse("P*K = " + std::to_string(P) + "*" + std::to_string(K) + " records of one row exceed the staging budget of " +
+               std::to_string(e->walkfwd_budget > 0 ? (size_t)e->walkfwd_budget : kWalkfwdBudget) + " bytes");
+    activate(e);
+    sync_all(e);
+    const bool select = steps || total;
+    const int32_t n_steps = select ? walkfwd_steps(K, train) : 0;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t chunk = (size_t)pl.rows_per_chunk, row_recs = (size_t)K * (size_t)P;
+    const size_t o_rec = pl.bounds_bytes, o_steps = o_rec + up(chunk * row_recs * sizeof(bt_fold));
+    e->d_walkfwd.ensure(o_steps + up(chunk * (size_t)n_steps * sizeof(bt_wf_step)));
+    uint8_t* base = e->d_walkfwd.p;
+    HIPCHK(hipMemcpyAsync(base, bounds, ((size_t)K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    WfArgs a{};
+    a.bounds = reinterpret_cast<const int32_t*>(base);
+    a.rec = reinterpret_cast<bt_fold*>(base + o_rec);
+    a.steps = reinterpret_cast<bt_wf_step*>(base + o_steps);
+    a.P = P, a.K = K;
+    a.train = train, a.j0 = std::max(train, 1), a.n_steps = n_steps;
+    std::vector<bt_fold> h_rec(folds ? chunk * row_recs : 0);       // device order [row][fold][param]
+    std::vector<bt_wf_step> own(!steps && total ? (size_t)S * (size_t)n_steps : 0);
+    bt_wf_step* st = steps ? steps : own.data();
+    for (size_t r0 = 0; r0 < (size_t)S; r0 += chunk) {
+        const size_t m = std::min(chunk, (size_t)S - r0);
+        a.syms = e->d_syms.p + r0;
+        a.n_rows = (int32_t)m;
+        HIPCHK(hipMemsetAsync(a.rec, 0, m * row_recs * sizeof(bt_fold), e->stream));
+        HIPCHK(launch_wf_walk(a, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, e->stream));
+        if (select) {
+            HIPCHK(launch_wf_select(a, e->grid, pl, e->stream));
+            HIPCHK(hipMemcpyAsync(st + r0 * (size_t)n_steps, a.steps, m * (size_t)n_steps * sizeof(bt_wf_step),
+                                  hipMemcpyDeviceToHost, e->stream));
+        }
+        if (folds)
+            HIPCHK(hipMemcpyAsync(h_rec.data(), a.rec, m * row_recs * sizeof(bt_fold), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (folds)   // [row][fold][param] -> the caller's [row][param][fold]
+            for (size_t r = 0; r < m; ++r)
+                for (size_t k = 0; k < (size_t)K; ++k)
+                    for (size_t p = 0; p < (size_t)P; ++p)
+                        folds[((r0 + r) * (size_t)P + p) * (size_t)K + k] = h_rec[(r * (size_t)K + k) * (size_t)P + p];
+    }
+    if (total) walkfwd_totals(S, n_steps, st, e->grid.sqrt_ann, total);
+    return 0;
+}
+
 void drain_timing(bt_engine* e) {
     for (auto& ev : e->ev_pending) {
         HIPCHK(hipEventSynchronize(ev.second));
@@ -875,6 +940,20 @@ int32_t bt_surface(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
 int32_t bt_surface_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* sym_ids,
                       bt_param_agg* agg, bt_topk_rec* best) {
     ABI_GUARD(-1, { return surface_of_impl(e, S, P, sum, sym_ids, agg, best); })
+}
+
+int32_t bt_walk_forward(bt_engine* e, int32_t K, const int32_t* bounds, int32_t train, bt_fold* folds,
+                        bt_wf_step* steps, bt_fold* total) {
+    ABI_GUARD(-1, { return walk_forward_impl(e, K, bounds, train, folds, steps, total); })
+}
+
+int32_t bt_set_walkfwd_budget(bt_engine* e, int64_t bytes) {
+    ABI_GUARD(-1, {
+        if (!e) throw HipFail{"bt_set_walkfwd_budget: null engine"};
+        if (bytes < 0) throw HipFail{"bt_set_walkfwd_budget: bytes = " + std::to_string(bytes) + " is negative"};
+        e->walkfwd_budget = bytes;
+        return 0;
+    })
 }
 
 int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks) {

@@ -164,6 +164,24 @@ struct ReplayOut {
 hipError_t launch_replay(const ReplayLane* lanes, int32_t n, const int32_t* high, const int32_t* low,
                          const int32_t* close, const Grid& g, const ReplayOut& o, hipStream_t st);
 
+// Walk-forward evaluation (k_walkfwd.hip, bt_walk_forward; docs/walkforward_spec.md) of one chunk
+// of dataset rows. The walk (one wave64 workgroup per (row, param)) cuts every lane's path into K
+// bar folds and leaves one bt_fold per (row, fold, param), params innermost so that the selection
+// (one workgroup per (row, step)) reads along p. The host zeroes `rec` before the walk, which
+// writes the records of non-empty folds and the first_bar of empty ones.
+struct WfArgs {
+    const SymDesc* syms;           // the chunk's rows
+    const int32_t* bounds;         // [K + 1] fold bounds, absolute bars
+    bt_fold* rec;                  // [n_rows][K][P]
+    bt_wf_step* steps;             // [n_rows][n_steps] (selection only)
+    int32_t n_rows, P, K;
+    int32_t train, j0, n_steps;    // selection: steps j = j0 .. K - 1
+};
+struct WalkfwdPlan;
+hipError_t launch_wf_walk(const WfArgs& a, const int32_t* high, const int32_t* low, const int32_t* close,
+                          const Grid& g, hipStream_t st);
+hipError_t launch_wf_select(const WfArgs& a, const Grid& g, const WalkfwdPlan& pl, hipStream_t st);
+
 // Reductions of an S x P summary matrix (k_surface.hip, bt_surface / bt_surface_of): one pass over
 // the records writes per-chunk column aggregates and per-tile row winners, two short kernels fold
 // them into agg[P] and best[S]. Symbol s has id ids[s * id_stride] (the engine's SymDesc array or

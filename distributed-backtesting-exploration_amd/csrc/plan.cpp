@@ -394,4 +394,29 @@ SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req) {
     return pl;
 }
 
+WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int cus, int64_t budget_req) {
+    // one grid index per (row, param) and per (row, step)
+    constexpr int64_t kMaxGrid = 1LL << 30;
+    WalkfwdPlan pl{};
+    S = std::max(S, 0);
+    P = std::max(P, 1);
+    K = std::max(K, 1);
+    const size_t budget = budget_req > 0 ? (size_t)budget_req : kWalkfwdBudget;
+    pl.bounds_bytes = (((size_t)K + 1) * sizeof(int32_t) + 255) & ~(size_t)255;
+    pl.row_bytes = (size_t)K * (size_t)P * sizeof(bt_fold) + (size_t)(K - 1) * sizeof(bt_wf_step);
+    // the records and the steps each start on a 256-byte boundary
+    const size_t fixed = pl.bounds_bytes + 2 * 256;
+    int64_t rows = budget > fixed ? (int64_t)((budget - fixed) / pl.row_bytes) : 0;
+    rows = std::min<int64_t>(rows, kMaxGrid / std::max(P, K));
+    rows = std::min<int64_t>(rows, S);
+    pl.rows_per_chunk = (int32_t)rows;
+    pl.chunks = rows > 0 ? (int32_t)((S + rows - 1) / rows) : 0;
+    pl.sel_block = 64 * std::min((P + 63) / 64, 4);
+    pl.tiles = (std::max(max_bars, 0) + kTile - 1) / kTile;
+    pl.waves = rows * P;
+    pl.fill = (double)pl.waves / ((double)std::max(cus, 1) * 4 * 8);
+    pl.staging_bytes = rows > 0 ? fixed + (size_t)rows * pl.row_bytes : 0;
+    return pl;
+}
+
 }  // namespace bt

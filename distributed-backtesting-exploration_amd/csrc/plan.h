@@ -72,4 +72,23 @@ struct SurfacePlan {
 // `chunks_req`: bt_set_surface_chunks (0 = automatic).
 SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req);
 
+// What a walk-forward evaluation (k_walkfwd.hip, bt_walk_forward) of S rows x P params x K folds is
+// launched with. The rows are processed in chunks of rows_per_chunk (the last one shorter): chunk c
+// holds rows [c * rows_per_chunk, min(S, (c + 1) * rows_per_chunk)), every row exactly once. A
+// chunk's device staging is the bounds, its fold records [rows][K][P] and its steps (sized for the
+// most a call can ask for, K - 1 per row), and never exceeds the budget. rows_per_chunk == 0: one
+// row alone does not fit, and the call is refused.
+constexpr size_t kWalkfwdBudget = 256u << 20;
+struct WalkfwdPlan {
+    int32_t rows_per_chunk, chunks;
+    int32_t sel_block;             // threads of a selection block (a multiple of 64, at most 256)
+    int32_t tiles;                 // 64-bar tiles the longest row's waves walk
+    int64_t waves;                 // walk workgroups (one wave each) of a full chunk
+    double fill;                   // ... in units of what the device holds at once (8 waves per SIMD)
+    size_t bounds_bytes, row_bytes;  // staging: the bounds (padded), and per row of a chunk
+    size_t staging_bytes;          // of a full chunk
+};
+// `budget_req`: bt_set_walkfwd_budget (0 = kWalkfwdBudget).
+WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int cus, int64_t budget_req = 0);
+
 }  // namespace bt

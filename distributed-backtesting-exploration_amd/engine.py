@@ -55,6 +55,19 @@ PARAM_AGG_DTYPE = np.dtype([
 ])
 assert PARAM_AGG_DTYPE.itemsize == 104
 SURFACE_OF_MAX = 1 << 22  # records Engine.surface_of stages (include/bt.h bt_surface_of)
+# include/bt.h bt_fold and bt_wf_step: one lane's result over one bar fold, and one walk-forward
+# step of one symbol (docs/walkforward_spec.md)
+FOLD_DTYPE = np.dtype([
+    ("first_bar", "<i4"), ("n_bars", "<i4"), ("n_trades", "<i4"), ("status", "<i4"),
+    ("pnl", "<i8"), ("mdd", "<i8"), ("exposure", "<i8"), ("sharpe", "<f8"),
+    ("s1_lo", "<u8"), ("s1_hi", "<i8"), ("s2_lo", "<u8"), ("s2_hi", "<i8"),
+])
+WF_STEP_DTYPE = np.dtype([
+    ("sym", "<i4"), ("fold", "<i4"), ("param", "<i4"), ("pad", "<i4"), ("train_sharpe", "<f8"),
+    ("oos", FOLD_DTYPE),
+])
+assert FOLD_DTYPE.itemsize == 80 and WF_STEP_DTYPE.itemsize == 104
+WALKFWD_FOLDS_MAX = 1 << 22  # fold records Engine.walk_forward(folds=True) returns
 
 
 class BtError(RuntimeError):
@@ -200,6 +213,11 @@ _LATE_SYMBOLS = {
     "bt_surface_host": (3, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                         C.c_int32),
     "bt_surface_merge": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], C.c_int32),
+    "bt_walk_forward": (3, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                            C.c_void_p], C.c_int32),
+    "bt_set_walkfwd_budget": (3, [C.c_void_p, C.c_int64], C.c_int32),
+    "bt_walk_forward_host": (3, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_void_p], C.c_int32),
 }
 _late = {}
 
@@ -431,6 +449,52 @@ def merge_surfaces(parts) -> Surface:
     return Surface(out[:P], best)
 
 
+@dataclass
+class WalkForward:
+    """Engine.walk_forward's result (bt_walk_forward, docs/walkforward_spec.md), rows in dataset
+    row order."""
+    bounds: np.ndarray | None     # int32[K + 1], the fold bounds (None from walk_forward_host)
+    train: int                    # training folds per step (0 = anchored)
+    steps: np.ndarray             # WF_STEP_DTYPE[S, n_steps]; Grid.param decodes steps["param"] >= 0
+    total: np.ndarray             # FOLD_DTYPE[S]: each row's out-of-sample folds as one record
+    folds: np.ndarray | None      # FOLD_DTYPE[S, P, K] when asked for
+
+    def oos_sharpe(self) -> np.ndarray:
+        """Per row, the Sharpe of its out-of-sample folds taken together (total["sharpe"])."""
+        return self.total["sharpe"].copy()
+
+    def train_sharpe(self) -> np.ndarray:
+        """[S, n_steps]: the training Sharpe each step's parameter was chosen with (0 where none)."""
+        return self.steps["train_sharpe"].copy()
+
+
+def _as_bounds(bounds) -> np.ndarray:
+    b = np.asarray(list(bounds) if not isinstance(bounds, np.ndarray) else bounds)
+    if b.ndim != 1 or not np.issubdtype(b.dtype, np.integer) or (len(b) and (b.min() < -2**31 or b.max() >= 2**31)):
+        raise ValueError("bounds: a 1-D sequence of int32 bar indices")
+    return np.ascontiguousarray(b, np.int32)
+
+
+def walk_forward_host(folds, sym_ids, train: int = 1, annualization: int = 252) -> WalkForward:
+    """bt_walk_forward_host: the steps and totals from fold records [S, P, K] on the CPU (no GPU
+    needed), the scalar restatement of Engine.walk_forward's selection."""
+    f = np.ascontiguousarray(folds, FOLD_DTYPE)
+    if f.ndim != 3:
+        raise ValueError("folds: an S x P x K array of FOLD_DTYPE")
+    S, P, K = f.shape
+    ids = np.ascontiguousarray(np.asarray(sym_ids, np.int32))
+    if ids.shape != (S,):
+        raise ValueError(f"sym_ids: {S} ids for {S} rows, got shape {ids.shape}")
+    n_steps = max(K - max(train, 1), 0)
+    steps = np.zeros((max(S, 1), max(n_steps, 1)), WF_STEP_DTYPE)
+    total = np.zeros(max(S, 1), FOLD_DTYPE)
+    _check(sym("bt_walk_forward_host")(S, P, K, train, f.ctypes.data if f.size else None,
+                                       ids.ctypes.data if S else None, annualization, steps.ctypes.data,
+                                       total.ctypes.data))
+    steps = np.ascontiguousarray(steps.reshape(-1)[:S * n_steps]).reshape(S, n_steps)
+    return WalkForward(None, train, steps, total[:S], f)
+
+
 class Engine:
     """One engine per GPU (one process per GPU)."""
 
@@ -617,6 +681,37 @@ class Engine:
         """Symbol chunks surface() cuts the rows into: 0 = the planner's choice, n = always n
         (clipped to the symbol count). Results are identical either way."""
         _check(sym("bt_set_surface_chunks")(self._h, n))
+
+    # ---- walk-forward evaluation (bt_walk_forward, k_walkfwd.hip)
+    def walk_forward(self, bounds, train: int = 1, folds: bool = False) -> WalkForward:
+        """Walk every (symbol, param) lane of the resident dataset once and cut its result into
+        the bar folds [bounds[k], bounds[k+1]); per symbol and step j = max(train, 1) .. K-1
+        choose the parameter with the best Sharpe over the `train` folds before fold j (all of
+        them when train == 0) and report that lane's record of fold j. With folds, every lane's
+        fold records come back too ([S, P, K], at most WALKFWD_FOLDS_MAX of them). run() need not
+        have been called."""
+        b = _as_bounds(bounds)
+        K = len(b) - 1
+        S = self.stats()["n_symbols"]
+        n_steps = max(K - max(train, 1), 0)
+        steps = np.zeros(max(S * n_steps, 1), WF_STEP_DTYPE)
+        total = np.zeros(max(S, 1), FOLD_DTYPE)
+        want = K >= 2  # a single fold has no step: only its records can be asked for
+        rec = None
+        if folds:
+            if S * self.n_params * max(K, 0) > WALKFWD_FOLDS_MAX:
+                raise BtError(f"bt_walk_forward: S*P*K = {S}*{self.n_params}*{K} exceeds 2^22 fold records")
+            rec = np.zeros(max(S * self.n_params * max(K, 0), 1), FOLD_DTYPE)
+        _check(sym("bt_walk_forward")(self._h, K, b.ctypes.data if len(b) else None, train,
+                                      None if rec is None else rec.ctypes.data,
+                                      steps.ctypes.data if want else None, total.ctypes.data if want else None))
+        return WalkForward(b, train, steps[:S * n_steps].reshape(S, n_steps), total[:S],
+                           None if rec is None else rec[:S * self.n_params * K].reshape(S, self.n_params, K))
+
+    def set_walkfwd_budget(self, nbytes: int) -> None:
+        """Device staging budget of walk_forward in bytes: 0 = the default (256 MB). Results are
+        identical whatever the budget."""
+        _check(sym("bt_set_walkfwd_budget")(self._h, nbytes))
 
     def stats(self) -> dict:
         st = _Stats()

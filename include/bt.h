@@ -270,6 +270,44 @@ int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks);
 int32_t bt_surface_host(int32_t S, int32_t P, const bt_summary* sum, const int32_t* sym_ids,
                         bt_param_agg* agg, bt_topk_rec* best);
 int32_t bt_surface_merge(const bt_param_agg* in, int32_t world, int32_t P, bt_param_agg* out);
+/* ---- walk-forward evaluation (k_walkfwd.hip, walkfwd.cpp; semantics: docs/walkforward_spec.md)
+ * Every (symbol, param) lane of the resident dataset is walked once over its whole series and its
+ * result is cut into K consecutive bar folds [bounds[k], bounds[k+1]) (absolute bar indices, clipped
+ * to each row's bars, common to every row). A step j = max(train, 1) .. K-1 chooses, per row, the
+ * parameter with the largest Sharpe over the training folds [j - train, j) ([0, j) when train == 0;
+ * ties to the lowest param) and reports that lane's record of fold j, which the choice never saw.
+ *   folds  [S][P][K] every lane's fold records (row-major), or NULL;
+ *   steps  [S][K - max(train, 1)] one bt_wf_step per row and step, or NULL;
+ *   total  [S] per row, the out-of-sample folds of its steps with param >= 0 as one record, or NULL.
+ * Synchronous like bt_replay: waits for the engine's streams, runs on the engine stream, copies
+ * back; bt_run need not have been called and nothing another entry point reads changes. Device
+ * staging is bounded by a fixed 256 MB budget: the rows are processed in chunks, never S*P*K.
+ * Added within ABI 3 (additive). Returns 0, or -1 with bt_last_error naming the offending value
+ * (the engine stays usable): a null engine, no dataset, K < 1, bounds not strictly increasing or
+ * bounds[0] < 0, train outside [0, K-1], steps or total with K < 2, all three outputs NULL, folds
+ * with S*P*K > 2^22, one row's P*K records larger than the staging budget. */
+typedef struct bt_fold {              /* 80 bytes */
+    int32_t first_bar, n_bars, n_trades, status;
+    int64_t pnl, mdd, exposure;       /* ticks, ticks, bars held */
+    double  sharpe;
+    uint64_t s1_lo; int64_t s1_hi; uint64_t s2_lo; int64_t s2_hi;  /* as bt_sums, of the fold */
+} bt_fold;
+typedef struct bt_wf_step {           /* 16 + 8 + 80 bytes */
+    int32_t sym, fold, param, pad;    /* global id, the out-of-sample fold j, chosen param or -1 */
+    double  train_sharpe;
+    bt_fold oos;
+} bt_wf_step;
+int32_t bt_walk_forward(bt_engine* e, int32_t K, const int32_t* bounds /* K + 1 */, int32_t train,
+                        bt_fold* folds, bt_wf_step* steps, bt_fold* total);
+/* Device staging budget of bt_walk_forward in bytes: 0 = the default (256 MB). Results are
+ * identical whatever the budget (tests force several chunks with a small one). */
+int32_t bt_set_walkfwd_budget(bt_engine* e, int64_t bytes);
+/* Host, no GPU needed: the steps and totals from fold records [S][P][K] (the scalar restatement of
+ * the device selection). annualization is bt_config.annualization. steps and/or total (not both
+ * NULL); K >= 2. */
+int32_t bt_walk_forward_host(int32_t S, int32_t P, int32_t K, int32_t train, const bt_fold* folds,
+                             const int32_t* sym_ids, int64_t annualization, bt_wf_step* steps,
+                             bt_fold* total);
 /* Average device time of the dominant kernel (BT_FLAG_TIMING), and how many launches. */
 int32_t bt_kernel_timing(bt_engine* e, double* total_ms, int64_t* launches, const char** name);
 int32_t bt_reset_timing(bt_engine* e);
