@@ -1,0 +1,247 @@
+// analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of and
+// bt_walk_forward with their two settings. Each call checks its arguments with the pure rules of
+// replay.h / surface.h / walkfwd.h, asks plan.h for its chunks and its staging layout, realises
+// that layout in the engine's one arena (engine_state.h), launches, and copies the results back
+// before it returns. Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "engine_state.h"
+#include "replay.h"
+#include "surface.h"
+#include "walkfwd.h"
+
+using namespace bt;
+
+namespace {
+
+[[noreturn]] void refuse(const char* fn, const std::string& why) { throw HipFail{std::string(fn) + ": " + why}; }
+
+// Every analysis call starts here, after its refusals: both streams drained, then the arena grown
+// to the call's plan. With the wait on the engine stream before the call returns this is the
+// invariant the shared arena rests on (engine_state.h).
+uint8_t* enter(bt_engine* e, size_t staging_bytes) {
+    activate(e);
+    sync_all(e);
+    e->d_arena.ensure(staging_bytes);
+    return e->d_arena.p;
+}
+
+// fn(first, count) for every chunk of `per` out of n items, in order; the last one may be shorter.
+template <class F>
+void for_chunks(size_t n, size_t per, F fn) {
+    for (size_t i0 = 0; i0 < n; i0 += per) fn(i0, std::min(per, n - i0));
+}
+
+// ---- bt_replay: chosen lanes again, with their trades and curves (k_replay.hip)
+int32_t replay_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
+                    int32_t* n_bars, bt_trade* trades, int64_t* equity, int8_t* pos, int64_t stride) {
+    const char* fn = "bt_replay";
+    if (!e) refuse(fn, "null engine");
+    std::string why = replay_refusal(!e->syms.empty(), n, trade_cap, trades != nullptr, lanes != nullptr, sum != nullptr);
+    if (!why.empty()) refuse(fn, why);
+    if (n == 0) return 0;
+    std::vector<ReplayLane> req;
+    int32_t W = 0;  // the longest requested symbol
+    why = replay_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, equity || pos, stride, req, W);
+    if (!why.empty()) refuse(fn, why);
+    const ReplayPlan pl = plan_replay(n, W, trade_cap, stride, equity != nullptr, pos != nullptr);
+    uint8_t* base = enter(e, pl.staging_bytes);
+    const size_t dcap = (size_t)pl.dcap, pitch = (size_t)pl.pitch;
+    ReplayLane* d_lanes = at<ReplayLane>(base, pl.o_lane);
+    ReplayOut out{};
+    out.sum = at<bt_summary>(base, pl.o_sum);
+    out.trades = dcap ? at<bt_trade>(base, pl.o_trades) : nullptr;
+    out.trade_cap = (int32_t)dcap;
+    out.equity = equity ? at<int64_t>(base, pl.o_equity) : nullptr;
+    out.pos = pos ? at<int8_t>(base, pl.o_pos) : nullptr;
+    out.pitch = pl.pitch;
+    // rows of a host array -> rows of a device one: one copy when the pitches agree, else a 2-D
+    // copy and the host tails zeroed here
+    auto fetch = [&](void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t m) {
+        if (dst_pitch == src_pitch) {
+            HIPCHK(hipMemcpyAsync(dst, src, m * src_pitch, hipMemcpyDeviceToHost, e->stream));
+            return;
+        }
+        HIPCHK(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, src_pitch, m, hipMemcpyDeviceToHost, e->stream));
+        for (size_t i = 0; i < m; ++i)
+            memset(static_cast<uint8_t*>(dst) + i * dst_pitch + src_pitch, 0, dst_pitch - src_pitch);
+    };
+    for_chunks((size_t)n, (size_t)pl.lanes_per_chunk, [&](size_t i0, size_t m) {
+        HIPCHK(hipMemcpyAsync(d_lanes, req.data() + i0, m * sizeof(ReplayLane), hipMemcpyHostToDevice, e->stream));
+        if (dcap) HIPCHK(hipMemsetAsync(out.trades, 0, m * dcap * sizeof(bt_trade), e->stream));
+        if (equity) HIPCHK(hipMemsetAsync(out.equity, 0, m * pitch * 8, e->stream));
+        if (pos) HIPCHK(hipMemsetAsync(out.pos, 0, m * pitch, e->stream));
+        HIPCHK(launch_replay(d_lanes, (int32_t)m, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, out, e->stream));
+        HIPCHK(hipMemcpyAsync(sum + i0, out.sum, m * sizeof(bt_summary), hipMemcpyDeviceToHost, e->stream));
+        if (dcap)
+            fetch(trades + i0 * (size_t)trade_cap, (size_t)trade_cap * sizeof(bt_trade), out.trades,
+                  dcap * sizeof(bt_trade), m);
+        if (equity) fetch(equity + i0 * (size_t)stride, (size_t)stride * 8, out.equity, pitch * 8, m);
+        if (pos) fetch(pos + i0 * (size_t)stride, (size_t)stride, out.pos, pitch, m);
+        HIPCHK(hipStreamSynchronize(e->stream));
+    });
+    if (n_bars)
+        for (int32_t i = 0; i < n; ++i) n_bars[i] = req[i].bars;
+    return n;
+}
+
+// ---- bt_surface / bt_surface_of: the run's summaries reduced on the device (k_surface.hip)
+// `d_sum` and `d_ids` are device pointers the engine's streams have finished writing; the pass and
+// its folds run on the engine stream and the results are copied back before the call returns.
+void surface_launch(bt_engine* e, const SurfacePlan& pl, uint8_t* base, const bt_summary* d_sum,
+                    const int32_t* d_ids, int32_t id_stride, int32_t S, int32_t P, bt_param_agg* agg,
+                    bt_topk_rec* best) {
+    SurfaceWork w{};
+    w.partial = at<bt_param_agg>(base, pl.o_partial);
+    w.fold = at<bt_param_agg>(base, pl.o_fold);
+    w.best_partial = at<bt_topk_rec>(base, pl.o_best_partial);
+    w.agg = agg ? at<bt_param_agg>(base, pl.o_agg) : nullptr;
+    w.best = best ? at<bt_topk_rec>(base, pl.o_best) : nullptr;
+    HIPCHK(launch_surface(d_sum, d_ids, id_stride, S, P, pl, w, e->stream));
+    // the results lie next to each other: one copy into pinned memory, whatever was asked for
+    const size_t n_agg = (size_t)P * sizeof(bt_param_agg), n_best = (size_t)S * sizeof(bt_topk_rec);
+    const size_t lo = agg ? pl.o_agg : pl.o_best, hi = best && S > 0 ? pl.o_best + n_best : pl.o_agg + n_agg;
+    if (hi <= lo) return;  // best alone of a matrix without rows
+    e->h_surface.ensure(hi - lo);
+    HIPCHK(hipMemcpyAsync(e->h_surface.p, base + lo, hi - lo, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (agg) memcpy(agg, e->h_surface.p + (pl.o_agg - lo), n_agg);
+    if (best && S > 0) memcpy(best, e->h_surface.p + (pl.o_best - lo), n_best);
+}
+
+int32_t surface_impl(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
+    const char* fn = "bt_surface";
+    if (!e) refuse(fn, "null engine");
+    if (!e->ran) refuse(fn, "no results");
+    uint64_t rows = 0;
+    for (const SymDesc& sd : e->syms) rows += (uint64_t)sd.bars;
+    const int32_t S = (int32_t)e->syms.size();
+    const std::string why = surface_refusal(S, e->P, agg || best, false, rows);
+    if (!why.empty()) refuse(fn, why);
+    const SurfacePlan pl = plan_surface(S, e->P, e->cus, e->surface_chunks);
+    uint8_t* base = enter(e, pl.staging_bytes);
+    // ids straight from the symbol descriptors: SymDesc is four int32 wide, the id its last
+    static_assert(sizeof(SymDesc) == 16 && offsetof(SymDesc, id) == 12, "SymDesc layout");
+    surface_launch(e, pl, base, e->d_sum[e->cur].p, reinterpret_cast<const int32_t*>(e->d_syms.p) + 3, 4, S,
+                   e->P, agg, best);
+    return 0;
+}
+
+int32_t surface_of_impl(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* ids,
+                        bt_param_agg* agg, bt_topk_rec* best) {
+    const char* fn = "bt_surface_of";
+    if (!e) refuse(fn, "null engine");
+    const std::string why = surface_refusal(S, P, agg || best, true, 0);
+    if (!why.empty()) refuse(fn, why);
+    if (S > 0 && (!sum || !ids)) refuse(fn, "sum and sym_ids are required");
+    const SurfacePlan pl = plan_surface(S, P, e->cus, e->surface_chunks, true);
+    uint8_t* base = enter(e, pl.staging_bytes);
+    bt_summary* d_sum = at<bt_summary>(base, pl.o_sum);
+    int32_t* d_ids = at<int32_t>(base, pl.o_ids);
+    if (S > 0) {
+        HIPCHK(hipMemcpyAsync(d_sum, sum, (size_t)S * (size_t)P * sizeof(bt_summary), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(d_ids, ids, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    }
+    surface_launch(e, pl, base, d_sum, d_ids, 1, S, P, agg, best);
+    return 0;
+}
+
+// ---- bt_walk_forward: every lane's folds and the out-of-sample picks (k_walkfwd.hip)
+// The rows go through the device in the chunks of the WalkfwdPlan: per chunk the records are
+// zeroed, walked, selected from and copied out; the totals are folded on the host (walkfwd.cpp).
+int32_t walk_forward_impl(bt_engine* e, int32_t K, const int32_t* bounds, int32_t train, bt_fold* folds,
+                          bt_wf_step* steps, bt_fold* total) {
+    const char* fn = "bt_walk_forward";
+    if (!e) refuse(fn, "null engine");
+    if (e->syms.empty()) refuse(fn, "no dataset loaded");
+    if (K >= 1 && !bounds) refuse(fn, "bounds are required");
+    const int32_t S = (int32_t)e->syms.size(), P = e->P;
+    const std::string why = walkfwd_refusal(K, bounds, train, folds != nullptr, steps != nullptr,
+                                            total != nullptr, S, P);
+    if (!why.empty()) refuse(fn, why);
+    const WalkfwdPlan pl = plan_walkfwd(S, P, K, e->max_bars, e->cus, e->walkfwd_budget);
+    if (pl.rows_per_chunk < 1)
+        refuse(fn, "P*K = " + std::to_string(P) + "*" + std::to_string(K) + " records of one row exceed the staging budget of " +
+                       std::to_string(e->walkfwd_budget > 0 ? (size_t)e->walkfwd_budget : kWalkfwdBudget) + " bytes");
+    uint8_t* base = enter(e, pl.staging_bytes);
+    const bool select = steps || total;
+    const int32_t n_steps = select ? walkfwd_steps(K, train) : 0;
+    const size_t row_recs = (size_t)K * (size_t)P;
+    HIPCHK(hipMemcpyAsync(base, bounds, ((size_t)K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    WfArgs a{};
+    a.bounds = at<const int32_t>(base, 0);
+    a.rec = at<bt_fold>(base, pl.o_rec);
+    a.steps = at<bt_wf_step>(base, pl.o_steps);
+    a.P = P, a.K = K;
+    a.train = train, a.j0 = std::max(train, 1), a.n_steps = n_steps;
+    std::vector<bt_fold> h_rec(folds ? (size_t)pl.rows_per_chunk * row_recs : 0);  // device order [row][fold][param]
+    std::vector<bt_wf_step> own(!steps && total ? (size_t)S * (size_t)n_steps : 0);
+    bt_wf_step* st = steps ? steps : own.data();
+    for_chunks((size_t)S, (size_t)pl.rows_per_chunk, [&](size_t r0, size_t m) {
+        a.syms = e->d_syms.p + r0;
+        a.n_rows = (int32_t)m;
+        HIPCHK(hipMemsetAsync(a.rec, 0, m * row_recs * sizeof(bt_fold), e->stream));
+        HIPCHK(launch_wf_walk(a, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, e->stream));
+        if (select) {
+            HIPCHK(launch_wf_select(a, e->grid, pl, e->stream));
+            HIPCHK(hipMemcpyAsync(st + r0 * (size_t)n_steps, a.steps, m * (size_t)n_steps * sizeof(bt_wf_step),
+                                  hipMemcpyDeviceToHost, e->stream));
+        }
+        if (folds)
+            HIPCHK(hipMemcpyAsync(h_rec.data(), a.rec, m * row_recs * sizeof(bt_fold), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (folds)   // [row][fold][param] -> the caller's [row][param][fold]
+            for (size_t r = 0; r < m; ++r)
+                for (size_t k = 0; k < (size_t)K; ++k)
+                    for (size_t p = 0; p < (size_t)P; ++p)
+                        folds[((r0 + r) * (size_t)P + p) * (size_t)K + k] = h_rec[(r * (size_t)K + k) * (size_t)P + p];
+    });
+    if (total) walkfwd_totals(S, n_steps, st, e->grid.sqrt_ann, total);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t bt_replay(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
+                  int32_t* n_bars, bt_trade* trades, int64_t* equity, int8_t* pos, int64_t stride) {
+    ABI_GUARD(-1, { return replay_impl(e, n, lanes, trade_cap, sum, n_bars, trades, equity, pos, stride); })
+}
+
+int32_t bt_surface(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
+    ABI_GUARD(-1, { return surface_impl(e, agg, best); })
+}
+
+int32_t bt_surface_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* sym_ids,
+                      bt_param_agg* agg, bt_topk_rec* best) {
+    ABI_GUARD(-1, { return surface_of_impl(e, S, P, sum, sym_ids, agg, best); })
+}
+
+int32_t bt_walk_forward(bt_engine* e, int32_t K, const int32_t* bounds, int32_t train, bt_fold* folds,
+                        bt_wf_step* steps, bt_fold* total) {
+    ABI_GUARD(-1, { return walk_forward_impl(e, K, bounds, train, folds, steps, total); })
+}
+
+int32_t bt_set_walkfwd_budget(bt_engine* e, int64_t bytes) {
+    ABI_GUARD(-1, {
+        if (!e) refuse("bt_set_walkfwd_budget", "null engine");
+        if (bytes < 0) refuse("bt_set_walkfwd_budget", "bytes = " + std::to_string(bytes) + " is negative");
+        e->walkfwd_budget = bytes;
+        return 0;
+    })
+}
+
+int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks) {
+    ABI_GUARD(-1, {
+        if (!e) refuse("bt_set_surface_chunks", "null engine");
+        if (chunks < 0) refuse("bt_set_surface_chunks", "chunks = " + std::to_string(chunks) + " is negative");
+        e->surface_chunks = chunks;
+        return 0;
+    })
+}
+
+}  // extern "C"

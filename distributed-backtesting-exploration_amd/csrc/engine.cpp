@@ -1,12 +1,11 @@
-// engine.cpp — the C ABI of include/bt.h: engine lifecycle, HBM-resident datasets, the
+// engine.cpp — the C ABI of include/bt.h but its analysis calls (analysis.cpp): engine lifecycle
+// (the engine itself is engine_state.h), HBM-resident datasets, runs and read-backs, the
 // JobsReply batch entry point (drop-in for process_incoming_job,
 // /root/reference/src/worker/process.rs:13-29); its host half, ingest and result strings, is batch.cpp.
 //
 // Nothing here computes a backtest on the CPU: every result comes from the HIP kernels in
 // k_*.hip. The host moves bars to HBM, launches and reads back; the HIP objects it holds are the
 // self-freeing types of hip_owned.h.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -14,16 +13,11 @@
 #include <cstring>
 #include <memory>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "batch.h"
 #include "csv.h"
-#include "hip_owned.h"
-#include "internal.h"
-#include "plan.h"
-#include "surface.h"
-#include "walkfwd.h"
+#include "engine_state.h"
 
 using namespace bt;
 
@@ -31,100 +25,7 @@ static thread_local std::string g_err;
 
 void bt::set_last_error(const std::string& s) { g_err = s; }
 
-constexpr int64_t kNtrRing = 64;  // per-run trade counter slots (bt_engine::d_ntr_ring)
-
-struct bt_engine {
-    bt_config cfg{};
-    std::vector<int32_t> ax[4];  // owned copies of the grid axes
-    Grid grid{};
-    int32_t P = 0;
-    // the engine stream (its own, or bt_config.stream borrowed) and the top-k chain stream (the
-    // chain of run i overlaps the kernel of run i+1). Declared before every buffer and event:
-    // members go in reverse order, so the streams outlive what was enqueued on them
-    Stream tstream, stream;
-    // What is still enqueued finishes before the members free what it uses. The engine stream is
-    // the first HIP object an engine makes: without it there is nothing to wait for.
-    ~bt_engine() {
-        if (!stream) return;
-        (void)hipSetDevice(cfg.device);
-        (void)hipStreamSynchronize(stream);
-        if (tstream) (void)hipStreamSynchronize(tstream);
-    }
-    DevBuf<int32_t> d_axes[4];
-    DevBuf<int32_t> d_kwin;      // SMA: Grid::kwin, Grid::krecip
-    DevBuf<double> d_krecip;
-    // dataset
-    std::vector<SymDesc> syms;
-    int64_t rows = 0;
-    DevBuf<SymDesc> d_syms;
-    DevBuf<int32_t> d_c, d_h, d_l;
-    // outputs, double-buffered: run i writes buffer i % 2 while the top-k chain of run i-1
-    // (on tstream) still reads the other one; `cur` is the buffer of the last run
-    DevBuf<bt_summary> d_sum[2];
-    DevBuf<uint64_t> d_key[2];
-    // per-run trade counters: a ring of kNtrRing slots, run r accumulating into slot
-    // r % kNtrRing; half the ring is zeroed every kNtrRing / 2 runs (slots last used >= 33 runs
-    // earlier), so a run enqueues no memset of its own. ntr[b]: the slot of the last run that
-    // wrote output buffer b
-    DevBuf<unsigned long long> d_ntr_ring;
-    unsigned long long* ntr[2] = {nullptr, nullptr};
-    int cur = 0;
-    int64_t nrun = 0;
-    DevBuf<bt_sums> d_sums;
-    DevBuf<bt_trade> d_trades;
-    int cus = kCusFallback;      // compute units of the device (launch plans, plan.h)
-    int32_t max_bars = 0;        // bars of the longest symbol
-    // bar segments: requested count (0 = auto, 1 = off) and burn-in tiles (0 = the strategy's
-    // default), the records of a split run and the count the last run used
-    int32_t seg_req = 0, burn_req = 0, seg_last = 1;
-    DevBuf<SegRec> d_seg;
-    DevBuf<double> d_segema;
-    DevBuf<unsigned long long> d_refixed;
-    DevBuf<unsigned long long> d_dbg;
-    Event ev_kdone;      // kernel of the last run finished (main stream)
-    Event ev_tdone[2];   // readers of buffer b finished (tstream)
-    bool tdone_armed[2] = {false, false};
-    // top-k work
-    DevBuf<unsigned int> d_hist, d_counts;
-    DevBuf<unsigned long long> d_state, d_above, d_cand;
-    DevBuf<bt_topk_rec> d_top;
-    PinnedBuf<bt_topk_rec> h_top;     // pinned host copy of d_top
-    // pipelined read-back slots: header + kTopkMax records + one record holding the trade count
-    PinnedBuf<bt_topk_rec> h_slot[BT_PIPE_SLOTS];
-    Event slot_ev[BT_PIPE_SLOTS];
-    bool slot_armed[BT_PIPE_SLOTS] = {};
-    bool topk_ready = false;          // top-k buffers allocated and their state initialised
-    bool ran = false;
-    // timing of the dominant kernel
-    std::vector<std::pair<Event, Event>> ev_pending, ev_pool;
-    double kernel_ms = 0.0;
-    int64_t launches = 0;
-    // bt_run_batch: pinned host staging of the columns in device row layout (c, h, l), the
-    // batch's summaries read back in one copy, phase events and the last batch's profile
-    PinnedBuf<int32_t> h_stage[3];
-    PinnedBuf<bt_summary> h_sum;
-    Event ev_batch[4];
-    bt_batch_profile prof{};
-    int64_t n_errors = 0;
-    // bt_replay: device staging of one chunk of requests (descriptors, summaries, trades, curves),
-    // at most kReplayBudget bytes whatever n and stride are
-    DevBuf<uint8_t> d_replay;
-    // bt_surface: requested row chunks (0 = the planner's choice), the partials and results of
-    // one reduction, and the matrix and ids bt_surface_of stages
-    int32_t surface_chunks = 0;
-    DevBuf<uint8_t> d_surface, d_surface_in;
-    PinnedBuf<uint8_t> h_surface;  // the results of one reduction
-    // bt_walk_forward: the staging budget asked for (0 = kWalkfwdBudget) and the device staging
-    // of one chunk of rows (bounds, fold records, steps), never more than the budget
-    int64_t walkfwd_budget = 0;
-    DevBuf<uint8_t> d_walkfwd;
-};
-
 namespace {
-
-void activate(bt_engine* e) { HIPCHK(hipSetDevice(e->cfg.device)); }
-
-bool has_hl(const bt_engine* e) { return e->cfg.strategy == BT_BOLL; }
 
 const char* kernel_name(int32_t strategy) {
     switch (strategy) {
@@ -176,8 +77,6 @@ void upload_grid(bt_engine* e) {
 
 static_assert(kStageAlign == kRowAlign, "batch.h lays staging rows out as the device columns");
 
-void sync_all(bt_engine* e);
-
 // Install a dataset: symbol descriptors (row offsets into the columns) and `rows` rows per
 // column; allocates the columns the strategy needs.
 void set_dataset(bt_engine* e, std::vector<SymDesc>&& syms, int64_t rows) {
@@ -219,11 +118,6 @@ void layout(bt_engine* e, int32_t n_sym, const int32_t* bars, const int64_t* ids
 TopkWork topk_work(bt_engine* e) {
     return TopkWork{e->d_hist.p, e->d_state.p, e->d_counts.p, e->d_above.p, e->d_cand.p,
                     kTopkCap, e->d_top.p + 1, reinterpret_cast<int32_t*>(e->d_top.p)};
-}
-
-void sync_all(bt_engine* e) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->tstream) HIPCHK(hipStreamSynchronize(e->tstream));
 }
 
 void ensure_outputs(bt_engine* e) {
@@ -339,231 +233,6 @@ void run_impl(bt_engine* e) {
         e->tdone_armed[b] = true;
     }
     e->ran = true;
-}
-
-// ---- bt_replay: chosen lanes again, with their trades and curves (k_replay.hip)
-// Device staging per call is bounded by this budget: the requests are processed in chunks of as
-// many lanes as fit (one lane of the longest symbol, 2^22 bars, with its curves and a full trade
-// list needs 37.7 + 134 MB, so one lane always fits).
-constexpr size_t kReplayBudget = 256u << 20;
-
-int32_t replay_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
-                    int32_t* n_bars, bt_trade* trades, int64_t* equity, int8_t* pos, int64_t stride) {
-    auto refuse = [](const std::string& m) { throw HipFail{"bt_replay: " + m}; };
-    if (!e) refuse("null engine");
-    if (e->syms.empty()) refuse("no dataset loaded");
-    if (n < 0 || n > BT_REPLAY_MAX)
-        refuse("n = " + std::to_string(n) + " outside [0, " + std::to_string(BT_REPLAY_MAX) + "]");
-    if (trade_cap < 0) refuse("trade_cap = " + std::to_string(trade_cap) + " is negative");
-    if (trades && trade_cap == 0) refuse("trades given with trade_cap = 0");
-    if (!trades && trade_cap > 0)
-        refuse("trade_cap = " + std::to_string(trade_cap) + " without a trades buffer");
-    if (n == 0) return 0;
-    if (!lanes || !sum) refuse("lanes and sum are required");
-    // global symbol id -> row; the first row of a repeated id wins
-    std::unordered_map<int32_t, int32_t> row;
-    row.reserve(e->syms.size());
-    for (size_t s = 0; s < e->syms.size(); ++s) row.emplace(e->syms[s].id, (int32_t)s);
-    std::vector<ReplayLane> req((size_t)n);
-    int32_t W = 0;  // the longest requested symbol
-    for (int32_t i = 0; i < n; ++i) {
-        const auto it = row.find(lanes[i].sym);
-        if (it == row.end())
-            refuse("unknown symbol id " + std::to_string(lanes[i].sym) + " (lane " + std::to_string(i) + ")");
-        if (lanes[i].param < 0 || lanes[i].param >= e->P)
-            refuse("param " + std::to_string(lanes[i].param) + " outside [0, " + std::to_string(e->P) +
-                   ") (lane " + std::to_string(i) + ")");
-        const SymDesc& sd = e->syms[(size_t)it->second];
-        req[i] = ReplayLane{sd.off, sd.bars, lanes[i].param};
-        W = std::max(W, sd.bars);
-    }
-    const bool curves = equity || pos;
-    if (curves && stride < W)
-        refuse("stride = " + std::to_string(stride) + " shorter than the longest requested symbol (" +
-               std::to_string(W) + " bars)");
-    activate(e);
-    sync_all(e);
-    // a lane closes at most one trade per bar: the device rows never need more than W slots
-    const int64_t dcap = std::min<int64_t>(trade_cap, W);
-    const int64_t pitch = curves ? std::min<int64_t>(stride, align_rows(W)) : 0;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t per_lane = sizeof(ReplayLane) + sizeof(bt_summary) + (size_t)dcap * sizeof(bt_trade) +
-                            (equity ? (size_t)pitch * 8 : 0) + (pos ? (size_t)pitch : 0);
-    const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, (kReplayBudget - 5 * 256) / per_lane));
-    const size_t o_lane = 0, o_sum = up(chunk * sizeof(ReplayLane));
-    const size_t o_tr = o_sum + up(chunk * sizeof(bt_summary));
-    const size_t o_eq = o_tr + up(chunk * (size_t)dcap * sizeof(bt_trade));
-    const size_t o_pos = o_eq + (equity ? up(chunk * (size_t)pitch * 8) : 0);
-    const size_t total = o_pos + (pos ? up(chunk * (size_t)pitch) : 0);
-    e->d_replay.ensure(total);
-    uint8_t* base = e->d_replay.p;
-    ReplayOut out{};
-    out.sum = reinterpret_cast<bt_summary*>(base + o_sum);
-    out.trades = dcap ? reinterpret_cast<bt_trade*>(base + o_tr) : nullptr;
-    out.trade_cap = (int32_t)dcap;
-    out.equity = equity ? reinterpret_cast<int64_t*>(base + o_eq) : nullptr;
-    out.pos = pos ? reinterpret_cast<int8_t*>(base + o_pos) : nullptr;
-    out.pitch = pitch;
-    // rows of a host array -> rows of a device one: one copy when the pitches agree, else a 2-D
-    // copy and the host tails zeroed here
-    auto fetch = [&](void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t m) {
-        if (dst_pitch == src_pitch) {
-            HIPCHK(hipMemcpyAsync(dst, src, m * src_pitch, hipMemcpyDeviceToHost, e->stream));
-            return;
-        }
-        HIPCHK(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, src_pitch, m, hipMemcpyDeviceToHost, e->stream));
-        for (size_t i = 0; i < m; ++i)
-            memset(static_cast<uint8_t*>(dst) + i * dst_pitch + src_pitch, 0, dst_pitch - src_pitch);
-    };
-    for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
-        const size_t m = std::min(chunk, (size_t)n - i0);
-        HIPCHK(hipMemcpyAsync(base + o_lane, req.data() + i0, m * sizeof(ReplayLane), hipMemcpyHostToDevice, e->stream));
-        if (dcap) HIPCHK(hipMemsetAsync(base + o_tr, 0, m * (size_t)dcap * sizeof(bt_trade), e->stream));
-        if (equity) HIPCHK(hipMemsetAsync(base + o_eq, 0, m * (size_t)pitch * 8, e->stream));
-        if (pos) HIPCHK(hipMemsetAsync(base + o_pos, 0, m * (size_t)pitch, e->stream));
-        HIPCHK(launch_replay(reinterpret_cast<const ReplayLane*>(base + o_lane), (int32_t)m, e->d_h.p, e->d_l.p,
-                             e->d_c.p, e->grid, out, e->stream));
-        HIPCHK(hipMemcpyAsync(sum + i0, out.sum, m * sizeof(bt_summary), hipMemcpyDeviceToHost, e->stream));
-        if (dcap)
-            fetch(trades + i0 * (size_t)trade_cap, (size_t)trade_cap * sizeof(bt_trade), out.trades,
-                  (size_t)dcap * sizeof(bt_trade), m);
-        if (equity) fetch(equity + i0 * (size_t)stride, (size_t)stride * 8, out.equity, (size_t)pitch * 8, m);
-        if (pos) fetch(pos + i0 * (size_t)stride, (size_t)stride, out.pos, (size_t)pitch, m);
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    if (n_bars)
-        for (int32_t i = 0; i < n; ++i) n_bars[i] = req[i].bars;
-    return n;
-}
-
-// ---- bt_surface / bt_surface_of: the run's summaries reduced on the device (k_surface.hip)
-// `d_sum` and `d_ids` are device pointers the engine's streams have finished writing; the pass and
-// its folds run on the engine stream and the results are copied back before the call returns.
-void surface_launch(bt_engine* e, const bt_summary* d_sum, const int32_t* d_ids, int32_t id_stride,
-                    int32_t S, int32_t P, bt_param_agg* agg, bt_topk_rec* best) {
-    const SurfacePlan pl = plan_surface(S, P, e->cus, e->surface_chunks);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_part = 0, o_fold = o_part + up(pl.partial_bytes);
-    const size_t o_bpart = o_fold + up(pl.fold_bytes);
-    const size_t o_agg = o_bpart + up(pl.best_partial_bytes);
-    const size_t o_best = o_agg + up((size_t)P * sizeof(bt_param_agg));
-    e->d_surface.ensure(o_best + up((size_t)S * sizeof(bt_topk_rec)) + 256);
-    uint8_t* base = e->d_surface.p;
-    SurfaceWork w{};
-    w.partial = reinterpret_cast<bt_param_agg*>(base + o_part);
-    w.fold = reinterpret_cast<bt_param_agg*>(base + o_fold);
-    w.best_partial = reinterpret_cast<bt_topk_rec*>(base + o_bpart);
-    w.agg = agg ? reinterpret_cast<bt_param_agg*>(base + o_agg) : nullptr;
-    w.best = best ? reinterpret_cast<bt_topk_rec*>(base + o_best) : nullptr;
-    HIPCHK(launch_surface(d_sum, d_ids, id_stride, S, P, pl, w, e->stream));
-    // the results lie next to each other: one copy into pinned memory, whatever was asked for
-    const size_t n_agg = (size_t)P * sizeof(bt_param_agg), n_best = (size_t)S * sizeof(bt_topk_rec);
-    const size_t lo = agg ? o_agg : o_best, hi = best && S > 0 ? o_best + n_best : o_agg + n_agg;
-    if (hi <= lo) return;  // best alone of a matrix without rows
-    e->h_surface.ensure(hi - lo);
-    HIPCHK(hipMemcpyAsync(e->h_surface.p, base + lo, hi - lo, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (agg) memcpy(agg, e->h_surface.p + (o_agg - lo), n_agg);
-    if (best && S > 0) memcpy(best, e->h_surface.p + (o_best - lo), n_best);
-}
-
-int32_t surface_impl(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
-    auto refuse = [](const std::string& m) { throw HipFail{"bt_surface: " + m}; };
-    if (!e) refuse("null engine");
-    if (!e->ran) refuse("no results");
-    uint64_t rows = 0;
-    for (const SymDesc& sd : e->syms) rows += (uint64_t)sd.bars;
-    const std::string why = surface_refusal((int64_t)e->syms.size(), e->P, agg || best, false, rows);
-    if (!why.empty()) refuse(why);
-    activate(e);
-    sync_all(e);
-    // ids straight from the symbol descriptors: SymDesc is four int32 wide, the id its last
-    static_assert(sizeof(SymDesc) == 16 && offsetof(SymDesc, id) == 12, "SymDesc layout");
-    surface_launch(e, e->d_sum[e->cur].p, reinterpret_cast<const int32_t*>(e->d_syms.p) + 3, 4,
-                   (int32_t)e->syms.size(), e->P, agg, best);
-    return 0;
-}
-
-int32_t surface_of_impl(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* ids,
-                        bt_param_agg* agg, bt_topk_rec* best) {
-    auto refuse = [](const std::string& m) { throw HipFail{"bt_surface_of: " + m}; };
-    if (!e) refuse("null engine");
-    const std::string why = surface_refusal(S, P, agg || best, true, 0);
-    if (!why.empty()) refuse(why);
-    if (S > 0 && (!sum || !ids)) refuse("sum and sym_ids are required");
-    activate(e);
-    sync_all(e);
-    const size_t n = (size_t)S * (size_t)P;
-    const size_t o_ids = (n * sizeof(bt_summary) + 255) & ~(size_t)255;
-    e->d_surface_in.ensure(o_ids + (size_t)S * sizeof(int32_t) + 256);
-    uint8_t* base = e->d_surface_in.p;
-    if (n) {
-        HIPCHK(hipMemcpyAsync(base, sum, n * sizeof(bt_summary), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipMemcpyAsync(base + o_ids, ids, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    }
-    surface_launch(e, reinterpret_cast<const bt_summary*>(base), reinterpret_cast<const int32_t*>(base + o_ids),
-                   1, S, P, agg, best);
-    return 0;
-}
-
-// ---- bt_walk_forward: every lane's folds and the out-of-sample picks (k_walkfwd.hip)
-// The rows go through the device in the chunks of the WalkfwdPlan: per chunk the records are
-// zeroed, walked, selected from and copied out; the totals are folded on the host (walkfwd.cpp).
-int32_t walk_forward_impl(bt_engine* e, int32_t K, const int32_t* bounds, int32_t train, bt_fold* folds,
-                          bt_wf_step* steps, bt_fold* total) {
-    auto refuse = [](const std::string& m) { throw HipFail{"bt_walk_forward: " + m}; };
-    if (!e) refuse("null engine");
-    if (e->syms.empty()) refuse("no dataset loaded");
-    if (K >= 1 && !bounds) refuse("bounds are required");
-    const int32_t S = (int32_t)e->syms.size(), P = e->P;
-    const std::string why = walkfwd_refusal(K, bounds, train, folds != nullptr, steps != nullptr,
-                                            total != nullptr, S, P);
-    if (!why.empty()) refuse(why);
-    const WalkfwdPlan pl = plan_walkfwd(S, P, K, e->max_bars, e->cus, e->walkfwd_budget);
-    if (pl.rows_per_chunk < 1)
-        refuse("P*K = " + std::to_string(P) + "*" + std::to_string(K) + " records of one row exceed the staging budget of " +
-               std::to_string(e->walkfwd_budget > 0 ? (size_t)e->walkfwd_budget : kWalkfwdBudget) + " bytes");
-    activate(e);
-    sync_all(e);
-    const bool select = steps || total;
-    const int32_t n_steps = select ? walkfwd_steps(K, train) : 0;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t chunk = (size_t)pl.rows_per_chunk, row_recs = (size_t)K * (size_t)P;
-    const size_t o_rec = pl.bounds_bytes, o_steps = o_rec + up(chunk * row_recs * sizeof(bt_fold));
-    e->d_walkfwd.ensure(o_steps + up(chunk * (size_t)n_steps * sizeof(bt_wf_step)));
-    uint8_t* base = e->d_walkfwd.p;
-    HIPCHK(hipMemcpyAsync(base, bounds, ((size_t)K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    WfArgs a{};
-    a.bounds = reinterpret_cast<const int32_t*>(base);
-    a.rec = reinterpret_cast<bt_fold*>(base + o_rec);
-    a.steps = reinterpret_cast<bt_wf_step*>(base + o_steps);
-    a.P = P, a.K = K;
-    a.train = train, a.j0 = std::max(train, 1), a.n_steps = n_steps;
-    std::vector<bt_fold> h_rec(folds ? chunk * row_recs : 0);       // device order [row][fold][param]
-    std::vector<bt_wf_step> own(!steps && total ? (size_t)S * (size_t)n_steps : 0);
-    bt_wf_step* st = steps ? steps : own.data();
-    for (size_t r0 = 0; r0 < (size_t)S; r0 += chunk) {
-        const size_t m = std::min(chunk, (size_t)S - r0);
-        a.syms = e->d_syms.p + r0;
-        a.n_rows = (int32_t)m;
-        HIPCHK(hipMemsetAsync(a.rec, 0, m * row_recs * sizeof(bt_fold), e->stream));
-        HIPCHK(launch_wf_walk(a, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, e->stream));
-        if (select) {
-            HIPCHK(launch_wf_select(a, e->grid, pl, e->stream));
-            HIPCHK(hipMemcpyAsync(st + r0 * (size_t)n_steps, a.steps, m * (size_t)n_steps * sizeof(bt_wf_step),
-                                  hipMemcpyDeviceToHost, e->stream));
-        }
-        if (folds)
-            HIPCHK(hipMemcpyAsync(h_rec.data(), a.rec, m * row_recs * sizeof(bt_fold), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (folds)   // [row][fold][param] -> the caller's [row][param][fold]
-            for (size_t r = 0; r < m; ++r)
-                for (size_t k = 0; k < (size_t)K; ++k)
-                    for (size_t p = 0; p < (size_t)P; ++p)
-                        folds[((r0 + r) * (size_t)P + p) * (size_t)K + k] = h_rec[(r * (size_t)K + k) * (size_t)P + p];
-    }
-    if (total) walkfwd_totals(S, n_steps, st, e->grid.sqrt_ann, total);
-    return 0;
 }
 
 void drain_timing(bt_engine* e) {
@@ -924,43 +593,6 @@ int32_t bt_read_close(bt_engine* e, int32_t sym_index, int32_t* out, int32_t n) 
         activate(e);
         sync_all(e);
         HIPCHK(hipMemcpy(out, e->d_c.p + sd.off, (size_t)n * 4, hipMemcpyDeviceToHost));
-        return 0;
-    })
-}
-
-int32_t bt_replay(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
-                  int32_t* n_bars, bt_trade* trades, int64_t* equity, int8_t* pos, int64_t stride) {
-    ABI_GUARD(-1, { return replay_impl(e, n, lanes, trade_cap, sum, n_bars, trades, equity, pos, stride); })
-}
-
-int32_t bt_surface(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
-    ABI_GUARD(-1, { return surface_impl(e, agg, best); })
-}
-
-int32_t bt_surface_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* sym_ids,
-                      bt_param_agg* agg, bt_topk_rec* best) {
-    ABI_GUARD(-1, { return surface_of_impl(e, S, P, sum, sym_ids, agg, best); })
-}
-
-int32_t bt_walk_forward(bt_engine* e, int32_t K, const int32_t* bounds, int32_t train, bt_fold* folds,
-                        bt_wf_step* steps, bt_fold* total) {
-    ABI_GUARD(-1, { return walk_forward_impl(e, K, bounds, train, folds, steps, total); })
-}
-
-int32_t bt_set_walkfwd_budget(bt_engine* e, int64_t bytes) {
-    ABI_GUARD(-1, {
-        if (!e) throw HipFail{"bt_set_walkfwd_budget: null engine"};
-        if (bytes < 0) throw HipFail{"bt_set_walkfwd_budget: bytes = " + std::to_string(bytes) + " is negative"};
-        e->walkfwd_budget = bytes;
-        return 0;
-    })
-}
-
-int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks) {
-    ABI_GUARD(-1, {
-        if (!e) throw HipFail{"bt_set_surface_chunks: null engine"};
-        if (chunks < 0) throw HipFail{"bt_set_surface_chunks: chunks = " + std::to_string(chunks) + " is negative"};
-        e->surface_chunks = chunks;
         return 0;
     })
 }

@@ -1,0 +1,121 @@
+// engine_state.h — the engine behind the C ABI's bt_engine handle and the helpers its entry points
+// share: engine.cpp (lifecycle, datasets, runs, batches) and analysis.cpp (replay, surface,
+// walk-forward). Private to the library and not part of the ABI: it includes HIP.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <utility>
+#include <vector>
+
+#include "hip_owned.h"
+#include "internal.h"
+#include "plan.h"
+
+namespace bt {
+
+constexpr int64_t kNtrRing = 64;  // per-run trade counter slots (EngineState::d_ntr_ring)
+
+struct EngineState {
+    bt_config cfg{};
+    std::vector<int32_t> ax[4];  // owned copies of the grid axes
+    Grid grid{};
+    int32_t P = 0;
+    // the engine stream (its own, or bt_config.stream borrowed) and the top-k chain stream (the
+    // chain of run i overlaps the kernel of run i+1). Declared before every buffer and event:
+    // members go in reverse order, so the streams outlive what was enqueued on them
+    Stream tstream, stream;
+    // What is still enqueued finishes before the members free what it uses. The engine stream is
+    // the first HIP object an engine makes: without it there is nothing to wait for.
+    ~EngineState() {
+        if (!stream) return;
+        (void)hipSetDevice(cfg.device);
+        (void)hipStreamSynchronize(stream);
+        if (tstream) (void)hipStreamSynchronize(tstream);
+    }
+    DevBuf<int32_t> d_axes[4];
+    DevBuf<int32_t> d_kwin;      // SMA: Grid::kwin, Grid::krecip
+    DevBuf<double> d_krecip;
+    // dataset
+    std::vector<SymDesc> syms;
+    int64_t rows = 0;
+    DevBuf<SymDesc> d_syms;
+    DevBuf<int32_t> d_c, d_h, d_l;
+    // outputs, double-buffered: run i writes buffer i % 2 while the top-k chain of run i-1
+    // (on tstream) still reads the other one; `cur` is the buffer of the last run
+    DevBuf<bt_summary> d_sum[2];
+    DevBuf<uint64_t> d_key[2];
+    // per-run trade counters: a ring of kNtrRing slots, run r accumulating into slot
+    // r % kNtrRing; half the ring is zeroed every kNtrRing / 2 runs (slots last used >= 33 runs
+    // earlier), so a run enqueues no memset of its own. ntr[b]: the slot of the last run that
+    // wrote output buffer b
+    DevBuf<unsigned long long> d_ntr_ring;
+    unsigned long long* ntr[2] = {nullptr, nullptr};
+    int cur = 0;
+    int64_t nrun = 0;
+    DevBuf<bt_sums> d_sums;
+    DevBuf<bt_trade> d_trades;
+    int cus = kCusFallback;      // compute units of the device (launch plans, plan.h)
+    int32_t max_bars = 0;        // bars of the longest symbol
+    // bar segments: requested count (0 = auto, 1 = off) and burn-in tiles (0 = the strategy's
+    // default), the records of a split run and the count the last run used
+    int32_t seg_req = 0, burn_req = 0, seg_last = 1;
+    DevBuf<SegRec> d_seg;
+    DevBuf<double> d_segema;
+    DevBuf<unsigned long long> d_refixed;
+    DevBuf<unsigned long long> d_dbg;
+    Event ev_kdone;      // kernel of the last run finished (main stream)
+    Event ev_tdone[2];   // readers of buffer b finished (tstream)
+    bool tdone_armed[2] = {false, false};
+    // top-k work
+    DevBuf<unsigned int> d_hist, d_counts;
+    DevBuf<unsigned long long> d_state, d_above, d_cand;
+    DevBuf<bt_topk_rec> d_top;
+    PinnedBuf<bt_topk_rec> h_top;     // pinned host copy of d_top
+    // pipelined read-back slots: header + kTopkMax records + one record holding the trade count
+    PinnedBuf<bt_topk_rec> h_slot[BT_PIPE_SLOTS];
+    Event slot_ev[BT_PIPE_SLOTS];
+    bool slot_armed[BT_PIPE_SLOTS] = {};
+    bool topk_ready = false;          // top-k buffers allocated and their state initialised
+    bool ran = false;
+    // timing of the dominant kernel
+    std::vector<std::pair<Event, Event>> ev_pending, ev_pool;
+    double kernel_ms = 0.0;
+    int64_t launches = 0;
+    // bt_run_batch: pinned host staging of the columns in device row layout (c, h, l), the
+    // batch's summaries read back in one copy, phase events and the last batch's profile
+    PinnedBuf<int32_t> h_stage[3];
+    PinnedBuf<bt_summary> h_sum;
+    Event ev_batch[4];
+    bt_batch_profile prof{};
+    int64_t n_errors = 0;
+    // The analysis calls (analysis.cpp: bt_replay, bt_surface, bt_surface_of, bt_walk_forward)
+    // share one device staging arena, grown to the staging_bytes of the current call's plan
+    // (plan.h), which lays it out. Sound because every analysis call is synchronous on the engine
+    // stream: it drains both streams on entry and the engine stream before it returns, so no two
+    // of them are in flight together and nothing reads the arena between calls.
+    DevBuf<uint8_t> d_arena;
+    int32_t surface_chunks = 0;    // bt_set_surface_chunks (0 = the planner's choice)
+    PinnedBuf<uint8_t> h_surface;  // the results of one reduction
+    int64_t walkfwd_budget = 0;    // bt_set_walkfwd_budget (0 = kWalkfwdBudget)
+};
+
+}  // namespace bt
+
+struct bt_engine : bt::EngineState {};  // the ABI's opaque handle
+
+namespace bt {
+
+inline void activate(bt_engine* e) { HIPCHK(hipSetDevice(e->cfg.device)); }
+
+inline bool has_hl(const bt_engine* e) { return e->cfg.strategy == BT_BOLL; }
+
+inline void sync_all(bt_engine* e) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->tstream) HIPCHK(hipStreamSynchronize(e->tstream));
+}
+
+// The one cast from a staging offset (plan.h Carve) to a typed device pointer.
+template <class T>
+T* at(uint8_t* base, size_t off) { return reinterpret_cast<T*>(base + off); }
+
+}  // namespace bt

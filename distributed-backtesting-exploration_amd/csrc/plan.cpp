@@ -1,12 +1,14 @@
 // plan.cpp — the host's launch decisions (plan.h): grid validation and ring sizing, block shapes,
-// bar segments, dynamic LDS and segment buffer sizes. Pure functions: no HIP call, no device
-// state; the profiling build's environment overrides sit next to the rules they override.
+// bar segments, dynamic LDS and segment buffer sizes, and the chunks and staging layouts of the
+// analysis calls. Pure functions: no HIP call, no device state; the profiling build's environment
+// overrides sit next to the rules they override.
 #include "plan.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
+#include "batch.h"
 #include "csv.h"
 #include "lds_layout.h"
 
@@ -365,7 +367,7 @@ LaunchPlan plan_launch(const Grid& g, const int32_t* ax0, const RunShape& r) {
 // kSurfaceWaves waves per SIMD. Every chunk writes one 104-B partial per parameter, a little more
 // than two records' worth, so a chunk keeps at least kSurfaceMinRows rows (partials then add at most
 // 104 / (16 x 48) = 14 % to the bytes moved) even when that leaves fewer waves.
-SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req) {
+SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req, bool staged) {
     constexpr int kSurfaceWaves = 4, kSurfaceMinRows = 16;
     constexpr int32_t kMaxGridY = 65535;
     SurfacePlan pl{};
@@ -391,6 +393,40 @@ SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req) {
     pl.partial_bytes = (size_t)pl.chunks * (size_t)P * sizeof(bt_param_agg);
     pl.fold_bytes = (size_t)pl.fold_ways * (size_t)P * sizeof(bt_param_agg);
     pl.best_partial_bytes = (size_t)S * (size_t)pl.p_tiles * sizeof(bt_topk_rec);
+    Carve c;
+    pl.o_partial = c.take(pl.partial_bytes);
+    pl.o_fold = c.take(pl.fold_bytes);
+    pl.o_best_partial = c.take(pl.best_partial_bytes);
+    pl.o_agg = c.take((size_t)P * sizeof(bt_param_agg));
+    pl.o_best = c.take((size_t)S * sizeof(bt_topk_rec));
+    pl.o_sum = c.take(staged ? (size_t)S * (size_t)P * sizeof(bt_summary) : 0);
+    pl.o_ids = c.take(staged ? (size_t)S * sizeof(int32_t) : 0);
+    pl.staging_bytes = c.staging_bytes();
+    return pl;
+}
+
+// ------------------------------------------------------------------------------- lane replay
+ReplayPlan plan_replay(int32_t n, int32_t W, int32_t trade_cap, int64_t stride, bool equity, bool pos,
+                       size_t budget_req) {
+    ReplayPlan pl{};
+    n = std::max(n, 0);
+    const size_t budget = budget_req > 0 ? budget_req : kReplayBudget;
+    pl.dcap = std::max<int64_t>(0, std::min<int64_t>(trade_cap, W));
+    pl.pitch = equity || pos ? std::min<int64_t>(stride, align_rows(W)) : 0;
+    const size_t per_lane = sizeof(ReplayLane) + sizeof(bt_summary) + (size_t)pl.dcap * sizeof(bt_trade) +
+                            (equity ? (size_t)pl.pitch * 8 : 0) + (pos ? (size_t)pl.pitch : 0);
+    // the five regions round up by less than kStagingAlign each: what is left holds whole lanes
+    const size_t pad = 5 * kStagingAlign;
+    const size_t lanes = std::min<size_t>((size_t)n, std::max<size_t>(1, budget > pad ? (budget - pad) / per_lane : 0));
+    pl.lanes_per_chunk = (int32_t)lanes;
+    pl.chunks = lanes ? (int32_t)(((size_t)n + lanes - 1) / lanes) : 0;
+    Carve c;
+    pl.o_lane = c.take(lanes * sizeof(ReplayLane));
+    pl.o_sum = c.take(lanes * sizeof(bt_summary));
+    pl.o_trades = c.take(lanes * (size_t)pl.dcap * sizeof(bt_trade));
+    pl.o_equity = c.take(equity ? lanes * (size_t)pl.pitch * 8 : 0);
+    pl.o_pos = c.take(pos ? lanes * (size_t)pl.pitch : 0);
+    pl.staging_bytes = c.staging_bytes();
     return pl;
 }
 
@@ -402,10 +438,13 @@ WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int 
     P = std::max(P, 1);
     K = std::max(K, 1);
     const size_t budget = budget_req > 0 ? (size_t)budget_req : kWalkfwdBudget;
-    pl.bounds_bytes = (((size_t)K + 1) * sizeof(int32_t) + 255) & ~(size_t)255;
-    pl.row_bytes = (size_t)K * (size_t)P * sizeof(bt_fold) + (size_t)(K - 1) * sizeof(bt_wf_step);
-    // the records and the steps each start on a 256-byte boundary
-    const size_t fixed = pl.bounds_bytes + 2 * 256;
+    Carve c;
+    c.take(((size_t)K + 1) * sizeof(int32_t));  // the bounds, at 0
+    pl.bounds_bytes = c.end;
+    const size_t rec_bytes = (size_t)K * (size_t)P * sizeof(bt_fold), step_bytes = (size_t)(K - 1) * sizeof(bt_wf_step);
+    pl.row_bytes = rec_bytes + step_bytes;
+    // the records and the steps each round up by less than kStagingAlign
+    const size_t fixed = pl.bounds_bytes + 2 * kStagingAlign;
     int64_t rows = budget > fixed ? (int64_t)((budget - fixed) / pl.row_bytes) : 0;
     rows = std::min<int64_t>(rows, kMaxGrid / std::max(P, K));
     rows = std::min<int64_t>(rows, S);
@@ -416,6 +455,8 @@ WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int 
     pl.waves = rows * P;
     pl.fill = (double)pl.waves / ((double)std::max(cus, 1) * 4 * 8);
     pl.staging_bytes = rows > 0 ? fixed + (size_t)rows * pl.row_bytes : 0;
+    pl.o_rec = c.take((size_t)rows * rec_bytes);
+    pl.o_steps = c.take((size_t)rows * step_bytes);
     return pl;
 }
 

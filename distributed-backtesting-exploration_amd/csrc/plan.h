@@ -1,7 +1,10 @@
 // plan.h — everything the host decides before a launch, as pure functions of the configuration,
 // the dataset shape and a CU count (plan.cpp). No HIP call, no device state: the engine
-// (engine.cpp) asks for a plan and sizes its buffers from it, the launchers (k_sma.hip,
-// k_tile.hip) enqueue what it says, and tests/plan/plan_driver.cpp prints it without a GPU.
+// (engine.cpp, analysis.cpp) asks for a plan and sizes its buffers from it, the launchers
+// (k_sma.hip, k_tile.hip) enqueue what it says, and tests/plan/*_driver.cpp print it without a GPU.
+// The plan of an analysis call (replay, surface, walk-forward) also owns the layout of the call's
+// device staging: the engine allocates staging_bytes, never fewer than 256 for a call it does not
+// refuse, and every region the plan names lies inside them.
 #pragma once
 #include "internal.h"
 
@@ -54,6 +57,39 @@ struct RunShape {
 // `ax0`: the host copy of the grid's first axis (Grid::a; the EMA burn-in follows its spans).
 LaunchPlan plan_launch(const Grid& g, const int32_t* ax0, const RunShape& r);
 
+// The one way a staging layout is made: regions taken one after the other, each starting on a
+// 256-byte boundary. take() returns the region's offset; `end` is the bytes carved so far.
+constexpr size_t kStagingAlign = 256;
+struct Carve {
+    size_t end = 0;
+    size_t take(size_t bytes) {
+        const size_t at = end;
+        end = at + (bytes + kStagingAlign - 1) / kStagingAlign * kStagingAlign;
+        return at;
+    }
+    size_t staging_bytes() const { return end > kStagingAlign ? end : kStagingAlign; }
+};
+
+// What a replay (k_replay.hip, bt_replay) of n lanes is launched with. The requests go through
+// the device in chunks of lanes_per_chunk (the last one shorter): chunk c holds lanes
+// [c * lanes_per_chunk, min(n, (c + 1) * lanes_per_chunk)), every lane exactly once. A chunk's
+// staging is bounded by the budget: as many lanes as fit, and one lane always fits the default
+// budget (a lane of the longest symbol, 2^22 bars, with its curves and a full trade list needs
+// 37.7 + 134 MB).
+constexpr size_t kReplayBudget = 256u << 20;
+struct ReplayPlan {
+    int64_t dcap;                  // trade slots per device row: a lane closes at most one trade per bar
+    int64_t pitch;                 // elements per device curve row (0 without curves)
+    int32_t lanes_per_chunk, chunks;
+    size_t o_lane, o_sum, o_trades, o_equity, o_pos;  // the regions of a chunk (o_equity, o_pos:
+                                   // empty when that curve is not wanted)
+    size_t staging_bytes;          // of a full chunk
+};
+// `W`: bars of the longest requested symbol; `budget_req`: 0 = kReplayBudget (tests only: the ABI
+// has no setter).
+ReplayPlan plan_replay(int32_t n, int32_t W, int32_t trade_cap, int64_t stride, bool equity, bool pos,
+                       size_t budget_req = 0);
+
 // What a reduction of an S x P summary matrix is launched with (k_surface.hip launch_surface).
 // Lanes run along p: grid x tiles the parameters in blocks of `block` threads, grid y cuts the
 // rows into `chunks`. Chunk c holds rows_per_chunk + (c < rows_rem) rows, starting at row
@@ -68,9 +104,14 @@ struct SurfacePlan {
     size_t partial_bytes;          // chunk aggregates: chunks x P bt_param_agg
     size_t fold_bytes;             // the first fold step's output: fold_ways x P bt_param_agg
     size_t best_partial_bytes;     // tile winners: S x p_tiles bt_topk_rec
+    // staging: the three work regions, then agg[P] and best[S] next to each other (one copy
+    // brings both back), then the matrix and ids a staged call (bt_surface_of) uploads
+    size_t o_partial, o_fold, o_best_partial, o_agg, o_best, o_sum, o_ids;
+    size_t staging_bytes;
 };
-// `chunks_req`: bt_set_surface_chunks (0 = automatic).
-SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req);
+// `chunks_req`: bt_set_surface_chunks (0 = automatic); `staged`: the layout holds the S x P matrix
+// and the S ids too.
+SurfacePlan plan_surface(int32_t S, int32_t P, int cus, int32_t chunks_req, bool staged = false);
 
 // What a walk-forward evaluation (k_walkfwd.hip, bt_walk_forward) of S rows x P params x K folds is
 // launched with. The rows are processed in chunks of rows_per_chunk (the last one shorter): chunk c
@@ -86,7 +127,8 @@ struct WalkfwdPlan {
     int64_t waves;                 // walk workgroups (one wave each) of a full chunk
     double fill;                   // ... in units of what the device holds at once (8 waves per SIMD)
     size_t bounds_bytes, row_bytes;  // staging: the bounds (padded), and per row of a chunk
-    size_t staging_bytes;          // of a full chunk
+    size_t staging_bytes;          // of a full chunk (0 with rows_per_chunk == 0)
+    size_t o_rec, o_steps;         // the chunk's records and steps; the bounds lie at 0
 };
 // `budget_req`: bt_set_walkfwd_budget (0 = kWalkfwdBudget).
 WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int cus, int64_t budget_req = 0);

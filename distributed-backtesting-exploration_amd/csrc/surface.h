@@ -1,5 +1,5 @@
 // surface.h — host side of the run reductions (docs/surface_spec.md): what surface.cpp shares with
-// engine.cpp. No HIP type: surface.cpp builds with a plain host compiler (tests/asan).
+// analysis.cpp. No HIP type: surface.cpp builds with a plain host compiler (tests/asan).
 #pragma once
 #include <stdint.h>
 

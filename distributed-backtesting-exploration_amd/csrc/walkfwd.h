@@ -1,5 +1,5 @@
 // walkfwd.h — host side of the walk-forward evaluation (docs/walkforward_spec.md): what walkfwd.cpp
-// shares with engine.cpp. No HIP type: walkfwd.cpp builds with a plain host compiler (tests/asan).
+// shares with analysis.cpp. No HIP type: walkfwd.cpp builds with a plain host compiler (tests/asan).
 #pragma once
 #include <stdint.h>
 

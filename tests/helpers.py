@@ -68,19 +68,49 @@ def compare_trades(gpu_tr, orc_tr, n, where=""):
     assert got == exp, f"{where}: trade lists differ (first diff at {next((i for i,(a,b) in enumerate(zip(got,exp)) if a!=b), None)})"
 
 
+CSRC = os.path.join(ROOT, "distributed-backtesting-exploration_amd", "csrc")
+SANITIZE = ("-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
+            "-Xarch_host", "-fno-omit-frame-pointer")
+# verify_asan_link_order=0: the environment may preload a library ahead of the ASan runtime
+SANITIZE_ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0")
+
+
 @functools.lru_cache(None)
-def _plan_driver():
-    """tests/plan/plan_driver.cpp and csrc/plan.cpp built once per session, the way the Makefile
-    compiles host files (host pass only: the planner makes no HIP call and needs no GPU)."""
-    csrc = os.path.join(ROOT, "distributed-backtesting-exploration_amd", "csrc")
-    exe = os.path.join(tempfile.mkdtemp(prefix="bt_plan_"), "plan_driver")
+def build_plan_driver(name, sources=("plan.cpp",), sanitize=False):
+    """tests/plan/<name>.cpp and the given csrc files built once per session, the way the Makefile
+    compiles host files (host pass only: the planner makes no HIP call and needs no GPU);
+    `sanitize`: as a stand-alone program under AddressSanitizer and UBSan."""
+    exe = os.path.join(tempfile.mkdtemp(prefix="bt_plan_"), name)
     atexit.register(shutil.rmtree, os.path.dirname(exe), True)
     r = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror",
-                        "-x", "hip", "--cuda-host-only", "-I", csrc, "-I", os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "tests", "plan", "plan_driver.cpp"),
-                        os.path.join(csrc, "plan.cpp"), "-o", exe], capture_output=True, text=True)
+                        *(SANITIZE if sanitize else ()), "-x", "hip", "--cuda-host-only", "-I", CSRC,
+                        "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "plan", name + ".cpp"),
+                        *(os.path.join(CSRC, s) for s in sources), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     return exe
+
+
+def run_driver(exe, *args, sanitized=False):
+    """One JSON line from a plan driver."""
+    r = subprocess.run([exe, *(str(a) for a in args)], capture_output=True, text=True, timeout=120,
+                       env=SANITIZE_ENV if sanitized else None)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    return json.loads(r.stdout)
+
+
+def assert_staging_layout(regions, staging_bytes, where=""):
+    """The rule of every analysis plan (csrc/plan.h): the regions, [(offset, bytes)] in layout
+    order, start on 256-byte boundaries, follow each other without overlap and end inside
+    staging_bytes, which is never below 256."""
+    end = 0
+    for i, (off, size) in enumerate(regions):
+        assert off % 256 == 0 and off >= end, f"{where}: region {i} at {off} after {end}"
+        end = off + size
+    assert max(end, 256) <= staging_bytes, f"{where}: regions end at {end}, staging {staging_bytes}"
+
+
+def _plan_driver():
+    return build_plan_driver("plan_driver")
 
 
 @functools.lru_cache(None)

@@ -3,7 +3,6 @@ bt_surface_merge against the plain-Python restatement of surface_ref.py on a lit
 adversarial matrices (surface_cases.py), the refusals, the record layout, the launch planner
 (plan_surface through tests/plan/surface_plan_driver.cpp), Surface's derived figures, and the host
 code as a stand-alone program under AddressSanitizer and UBSan (tests/asan/surface_driver.cpp)."""
-import functools
 import json
 import os
 import re
@@ -15,6 +14,7 @@ import pytest
 
 import dbx_amd as D
 from dbx_amd import engine as E
+from helpers import assert_staging_layout, build_plan_driver, run_driver
 from surface_cases import SHAPES, adversarial, adversarial_ref, assert_same
 from surface_ref import PARAM_AGG, SUMMARY, TOPK, qs, surface_ref, ties
 
@@ -202,25 +202,12 @@ def test_param_agg_layout(tmp_path):
 
 
 # ---------------------------------------------------------------------------------- planner
-@functools.lru_cache(None)
-def _surface_plan_driver(tmp):
-    exe = os.path.join(tmp, "surface_plan_driver")
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror",
-                        "-x", "hip", "--cuda-host-only", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "tests", "plan", "surface_plan_driver.cpp"),
-                        os.path.join(CSRC, "plan.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = _surface_plan_driver(str(tmp_path_factory.mktemp("surface_plan")))
+def plan():
+    exe = build_plan_driver("surface_plan_driver")
 
-    def run(S, P, cus=256, chunks=0):
-        out = subprocess.run([exe, str(S), str(P), str(cus), str(chunks)], capture_output=True, text=True,
-                             check=True).stdout
-        return json.loads(out)
+    def run(S, P, cus=256, chunks=0, staged=0):
+        return run_driver(exe, S, P, cus, chunks, staged)
     return run
 
 
@@ -254,6 +241,24 @@ def test_plan_surface_covers_every_row_once(plan, name):
     assert max(r1 - r0 for r0, r1 in rows) - min(r1 - r0 for r0, r1 in rows) <= 1
     if req:
         assert pl["chunks"] == max(1, min(req, S))
+    # the staging layout: the work regions, the two results next to each other (one copy brings
+    # both back), and for bt_surface_of the matrix and the ids in the same layout
+    for staged in (0, 1):
+        st = plan(S, P, 256, req, staged)
+        assert {k: v for k, v in st.items() if not k.startswith("o_") and k != "staging_bytes"} == \
+            {k: v for k, v in pl.items() if not k.startswith("o_") and k != "staging_bytes"}
+        assert_staging_layout([(st["o_partial"], st["partial_bytes"]), (st["o_fold"], st["fold_bytes"]),
+                               (st["o_best_partial"], st["best_partial_bytes"]), (st["o_agg"], P * 104),
+                               (st["o_best"], S * 24), (st["o_sum"], staged * S * P * 48), (st["o_ids"], staged * S * 4)],
+                              st["staging_bytes"], f"{name} staged {staged}")
+        assert st["o_best"] - (st["o_agg"] + P * 104) < 256
+        assert st["staging_bytes"] < st["o_ids"] + staged * S * 4 + 512, "no more than the regions need"
+
+
+def test_plan_driver_under_asan_and_ubsan():
+    exe = build_plan_driver("surface_plan_driver", sanitize=True)
+    assert run_driver(exe, 65, 130, 256, 3, 1, sanitized=True) == \
+        run_driver(build_plan_driver("surface_plan_driver"), 65, 130, 256, 3, 1)
 
 
 def test_plan_surface_fills_the_gpu_without_shredding_the_rows(plan):

@@ -3,7 +3,6 @@ walkfwd_ref.py pinned to the C oracle's whole-series figures, bt_walk_forward_ho
 reference byte for byte, its refusals, the record layouts, the chunk planner (plan_walkfwd through
 tests/plan/walkfwd_plan_driver.cpp) and the host code as a stand-alone program under
 AddressSanitizer and UBSan (tests/asan/walkfwd_driver.cpp)."""
-import functools
 import json
 import os
 import re
@@ -17,6 +16,7 @@ import dbx_amd as D
 from dbx_amd import engine as E
 import orc_ffi as F
 import walkfwd_ref as R
+from helpers import assert_staging_layout, build_plan_driver, run_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "distributed-backtesting-exploration_amd", "csrc")
@@ -172,25 +172,12 @@ def test_record_layouts(tmp_path):
 
 
 # ------------------------------------------------------------------------------ (d) planner
-@functools.lru_cache(None)
-def _plan_driver(tmp):
-    exe = os.path.join(tmp, "walkfwd_plan_driver")
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror",
-                        "-x", "hip", "--cuda-host-only", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "tests", "plan", "walkfwd_plan_driver.cpp"),
-                        os.path.join(CSRC, "plan.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    exe = _plan_driver(str(tmp_path_factory.mktemp("walkfwd_plan")))
+def plan():
+    exe = build_plan_driver("walkfwd_plan_driver")
 
     def run(S, P, K, bars=2520, cus=256, budget=0):
-        out = subprocess.run([exe] + [str(x) for x in (S, P, K, bars, cus, budget)], capture_output=True,
-                             text=True, check=True).stdout
-        return json.loads(out)
+        return run_driver(exe, S, P, K, bars, cus, budget)
     return run
 
 
@@ -213,10 +200,12 @@ def test_plan_walkfwd_covers_every_row_once_within_the_budget(plan, name):
     assert pl["bounds_bytes"] >= (K + 1) * 4 and pl["bounds_bytes"] % 256 == 0
     rpc = pl["rows_per_chunk"]
     assert 1 <= rpc <= S
-    # what the engine allocates: the bounds, the records and the steps, each on a 256-byte boundary
-    up = lambda b: (b + 255) & ~255
-    alloc = pl["bounds_bytes"] + up(rpc * K * P * 80) + up(rpc * (K - 1) * 104)
-    assert alloc <= pl["staging_bytes"] <= budget
+    # the engine allocates staging_bytes: the plan's own regions (the bounds, a full chunk's records
+    # and steps) lie inside them, and they inside the budget
+    assert pl["o_rec"] == pl["bounds_bytes"]
+    assert_staging_layout([(0, (K + 1) * 4), (pl["o_rec"], rpc * K * P * 80), (pl["o_steps"], rpc * (K - 1) * 104)],
+                          pl["staging_bytes"], name)
+    assert pl["staging_bytes"] <= budget
     # as many rows as fit: one more row would pass the budget (or there is no more row)
     assert rpc == S or pl["staging_bytes"] + pl["row_bytes"] > budget
     assert pl["chunks"] == -(-S // rpc)
@@ -239,6 +228,13 @@ def test_plan_walkfwd_on_the_shapes_of_the_issue(plan):
     # one row that cannot fit: the plan says so with rows_per_chunk 0 and the call is refused
     assert plan(3, 1 << 20, 4)["rows_per_chunk"] == 0
     assert plan(3, 400, 10, 2520, 256, 1000)["rows_per_chunk"] == 0
+
+
+def test_plan_driver_under_asan_and_ubsan():
+    exe = build_plan_driver("walkfwd_plan_driver", sanitize=True)
+    S, P, K, bars, req = PLAN_SHAPES["one_row_chunks"]
+    assert run_driver(exe, S, P, K, bars, 256, req, sanitized=True) == \
+        run_driver(build_plan_driver("walkfwd_plan_driver"), S, P, K, bars, 256, req)
 
 
 # ---------------------------------------------------------------------- (e) under the sanitizers
