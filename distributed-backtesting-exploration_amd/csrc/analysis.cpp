@@ -1,8 +1,8 @@
-// analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of and
-// bt_walk_forward with their two settings. Each call checks its arguments with the pure rules of
-// replay.h / surface.h / walkfwd.h, asks plan.h for its chunks and its staging layout, realises
-// that layout in the engine's one arena (engine_state.h), launches, and copies the results back
-// before it returns. Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
+// analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of, bt_topk_of
+// and bt_walk_forward with their two settings. Each call checks its arguments with the pure rules of
+// replay.h / surface.h / topk_rules.h / walkfwd.h, asks plan.h for its chunks and its staging
+// layout, realises that layout in the engine's one arena (engine_state.h), launches, and copies the
+// results back before it returns. Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -11,6 +11,7 @@
 #include "engine_state.h"
 #include "replay.h"
 #include "surface.h"
+#include "topk_rules.h"
 #include "walkfwd.h"
 
 using namespace bt;
@@ -149,6 +150,48 @@ int32_t surface_of_impl(bt_engine* e, int32_t S, int32_t P, const bt_summary* su
     return 0;
 }
 
+// ---- bt_topk_of: the run's top-k chain (k_topk.hip) on a caller's records
+// The keys are what a strategy kernel would have left beside these summaries (order_key of the
+// Sharpe), the descriptors carry the ids alone (the chain reads nothing else of them), and the
+// TopkWork is the call's own, in the arena: the engine's d_top, its selection state and its key
+// buffers stay as the last run left them.
+int32_t topk_of_impl(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* ids, int32_t k,
+                     int32_t lds_free_hist, bt_topk_rec* out) {
+    static_assert(kTopkOfMaxK == kTopkMax, "topk_rules.h restates kTopkMax");
+    const char* fn = "bt_topk_of";
+    if (!e) refuse(fn, "null engine");
+    const std::string why = topk_of_refusal(S, P, k, sum != nullptr, ids, out != nullptr);
+    if (!why.empty()) refuse(fn, why);
+    const size_t n = (size_t)S * (size_t)P;
+    std::vector<uint64_t> key(n);
+    for (size_t i = 0; i < n; ++i) key[i] = order_key(sum[i].sharpe);
+    std::vector<SymDesc> syms((size_t)S);
+    for (int32_t s = 0; s < S; ++s) syms[s] = SymDesc{0, 0, ids[s]};
+    const TopkOfPlan pl = plan_topk_of(S, P);
+    uint8_t* base = enter(e, pl.staging_bytes);
+    uint64_t* d_key = at<uint64_t>(base, pl.o_key);
+    bt_summary* d_sum = at<bt_summary>(base, pl.o_sum);
+    SymDesc* d_syms = at<SymDesc>(base, pl.o_syms);
+    bt_topk_rec* d_out = at<bt_topk_rec>(base, pl.o_out);  // [0]: the count, then the records
+    const TopkWork w{at<unsigned int>(base, pl.o_hist),      at<unsigned long long>(base, pl.o_state),
+                     at<unsigned int>(base, pl.o_counts),    at<unsigned long long>(base, pl.o_above),
+                     at<unsigned long long>(base, pl.o_cand), kTopkCap, d_out + 1, reinterpret_cast<int32_t*>(d_out)};
+    HIPCHK(hipMemcpyAsync(d_key, key.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(d_sum, sum, n * sizeof(bt_summary), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(d_syms, syms.data(), (size_t)S * sizeof(SymDesc), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(d_out, 0, ((size_t)kTopkMax + 1) * sizeof(bt_topk_rec), e->stream));
+    HIPCHK(launch_topk_init(w, e->stream));
+    HIPCHK(launch_topk(d_key, d_sum, d_syms, (int64_t)n, P, k, w, e->stream, lds_free_hist != 0));
+    std::vector<bt_topk_rec> got((size_t)k + 1);
+    HIPCHK(hipMemcpyAsync(got.data(), d_out, got.size() * sizeof(bt_topk_rec), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    int32_t count;
+    memcpy(&count, &got[0], sizeof count);
+    if (count < 0 || count > k) refuse(fn, "the device wrote a count of " + std::to_string(count));
+    memcpy(out, got.data() + 1, (size_t)count * sizeof(bt_topk_rec));
+    return count;
+}
+
 // ---- bt_walk_forward: every lane's folds and the out-of-sample picks (k_walkfwd.hip)
 // The rows go through the device in the chunks of the WalkfwdPlan: per chunk the records are
 // zeroed, walked, selected from and copied out; the totals are folded on the host (walkfwd.cpp).
@@ -219,6 +262,11 @@ int32_t bt_surface(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best) {
 int32_t bt_surface_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* sym_ids,
                       bt_param_agg* agg, bt_topk_rec* best) {
     ABI_GUARD(-1, { return surface_of_impl(e, S, P, sum, sym_ids, agg, best); })
+}
+
+int32_t bt_topk_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, const int32_t* sym_ids, int32_t k,
+                   int32_t lds_free_hist, bt_topk_rec* out) {
+    ABI_GUARD(-1, { return topk_of_impl(e, S, P, sum, sym_ids, k, lds_free_hist, out); })
 }
 
 int32_t bt_walk_forward(bt_engine* e, int32_t K, const int32_t* bounds, int32_t train, bt_fold* folds,

@@ -18,6 +18,7 @@
 #include "batch.h"
 #include "csv.h"
 #include "engine_state.h"
+#include "topk_rules.h"
 
 using namespace bt;
 
@@ -439,6 +440,10 @@ int32_t bt_load_ohlc(bt_engine* e, int32_t n_sym, const int64_t* sym_ids, const 
         if (has_hl(e) && (!h || !l)) throw HipFail{"strategy needs high and low columns"};
         for (int32_t s = 0; s < n_sym; ++s)
             if (bars[s] < 1 || bars[s] > kMaxBars) throw HipFail{"bad bar count"};
+        // the id rule (topk_rules.h), before anything is laid out: a refused call leaves the
+        // resident dataset as it was
+        const std::string bad_id = sym_id_refusal(n_sym, sym_ids);
+        if (!bad_id.empty()) throw HipFail{"bt_load_ohlc: " + bad_id};
         activate(e);
         sync_all(e);  // the pinned staging may still feed an earlier upload
         layout(e, n_sym, bars, sym_ids);

@@ -279,6 +279,9 @@ __host__ __device__ inline double i128_to_double(uint64_t lo, int64_t hi) {
     return neg ? -r : r;
 }
 
+// The order of bt_topk_rec on the host (bt_merge_topk, comm.cpp merge_block). Ids compare as int32
+// here and as unsigned words on the device (k_topk.hip sym_param): one order, because every symbol
+// id lies in [0, 2^31) (topk_rules.h).
 inline bool topk_less(const bt_topk_rec& a, const bt_topk_rec& b) {
     const uint64_t ka = order_key(a.sharpe), kb = order_key(b.sharpe);
     if (ka != kb) return ka > kb;

@@ -127,7 +127,9 @@ __global__ __launch_bounds__(256) void topk_collect(const uint64_t* __restrict__
     }
 }
 
-// (sym id, param) of record idx, the tie-break order (ascending) as one 64-bit word.
+// (sym id, param) of record idx, the tie-break order (ascending) as one 64-bit word. The id enters
+// as an unsigned word while the host compares ids as int32 (internal.h topk_less): the same order,
+// because every symbol id lies in [0, 2^31) (topk_rules.h: the loaders refuse any other).
 __device__ __forceinline__ uint64_t sym_param(const SymDesc* __restrict__ syms, int32_t P,
                                               unsigned long long idx) {
     // 32-bit division whenever the index fits (a 64-bit one is a long software sequence)

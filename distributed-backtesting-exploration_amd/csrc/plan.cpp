@@ -460,4 +460,22 @@ WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int 
     return pl;
 }
 
+// ---------------------------------------------------------------------- top-k of given records
+TopkOfPlan plan_topk_of(int32_t S, int32_t P) {
+    TopkOfPlan pl{};
+    const size_t rows = (size_t)std::max(S, 0), n = rows * (size_t)std::max(P, 1);
+    Carve c;
+    pl.o_key = c.take(n * sizeof(uint64_t));
+    pl.o_sum = c.take(n * sizeof(bt_summary));
+    pl.o_syms = c.take(rows * sizeof(SymDesc));
+    pl.o_hist = c.take(4096 * sizeof(unsigned int));
+    pl.o_state = c.take(4 * sizeof(unsigned long long));
+    pl.o_counts = c.take(2 * sizeof(unsigned int));
+    pl.o_above = c.take((size_t)kTopkCap * sizeof(unsigned long long));
+    pl.o_cand = c.take((size_t)kTopkCap * sizeof(unsigned long long));
+    pl.o_out = c.take(((size_t)kTopkMax + 1) * sizeof(bt_topk_rec));
+    pl.staging_bytes = c.staging_bytes();
+    return pl;
+}
+
 }  // namespace bt

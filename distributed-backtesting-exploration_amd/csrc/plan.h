@@ -133,4 +133,16 @@ struct WalkfwdPlan {
 // `budget_req`: bt_set_walkfwd_budget (0 = kWalkfwdBudget).
 WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int cus, int64_t budget_req = 0);
 
+// The staging of a top-k chain over a caller's S x P records (k_topk.hip, bt_topk_of): what the
+// call uploads (order keys, summaries, one SymDesc per row) and a TopkWork of its own, so that the
+// engine's own top-k buffers are never touched: the 4,096-bin histogram, the selection state,
+// the two counts, kTopkCap indices above the selected prefix and kTopkCap candidates, and the
+// result with its count in front (kTopkMax + 1 records).
+struct TopkOfPlan {
+    size_t o_key, o_sum, o_syms;
+    size_t o_hist, o_state, o_counts, o_above, o_cand, o_out;
+    size_t staging_bytes;
+};
+TopkOfPlan plan_topk_of(int32_t S, int32_t P);
+
 }  // namespace bt

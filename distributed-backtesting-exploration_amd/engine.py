@@ -55,6 +55,7 @@ PARAM_AGG_DTYPE = np.dtype([
 ])
 assert PARAM_AGG_DTYPE.itemsize == 104
 SURFACE_OF_MAX = 1 << 22  # records Engine.surface_of stages (include/bt.h bt_surface_of)
+TOPK_OF_MAX = 1 << 22  # records Engine.topk_of stages (include/bt.h bt_topk_of)
 # include/bt.h bt_fold and bt_wf_step: one lane's result over one bar fold, and one walk-forward
 # step of one symbol (docs/walkforward_spec.md)
 FOLD_DTYPE = np.dtype([
@@ -209,6 +210,8 @@ _LATE_SYMBOLS = {
     "bt_surface": (3, [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
     "bt_surface_of": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.c_void_p], C.c_int32),
+    "bt_topk_of": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                       C.c_void_p], C.c_int32),
     "bt_set_surface_chunks": (3, [C.c_void_p, C.c_int32], C.c_int32),
     "bt_surface_host": (3, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                         C.c_int32),
@@ -676,6 +679,18 @@ class Engine:
                                     ids.ctypes.data if S else None, agg.ctypes.data,
                                     None if rec is None else rec.ctypes.data))
         return Surface(agg[:P], None if rec is None else rec[:S])
+
+    def topk_of(self, summaries, sym_ids, k: int, lds_free_hist: bool = False) -> np.ndarray:
+        """The run's top-k chain (bt_topk_of, k_topk.hip) on a caller's S x P summary matrix (at
+        most TOPK_OF_MAX records) and its symbol ids: the min(k, S*P) best records, as read_topk()
+        returns them. lds_free_hist: the histogram kernel without LDS (up to 2^18 records)."""
+        m, ids = _as_matrix(summaries, sym_ids)
+        S, P = m.shape
+        out = np.zeros(max(k, 1), TOPK_DTYPE)
+        n = _check(sym("bt_topk_of")(self._h, S, P, m.ctypes.data if m.size else None,
+                                     ids.ctypes.data if S else None, k, int(bool(lds_free_hist)),
+                                     out.ctypes.data))
+        return out[:n]
 
     def set_surface_chunks(self, n: int) -> None:
         """Symbol chunks surface() cuts the rows into: 0 = the planner's choice, n = always n

@@ -113,7 +113,9 @@ typedef struct bt_sums {
     int64_t s2_hi;
 } bt_sums;
 
-/* Global top-k record (24 B): ordered by sharpe desc, then sym asc, then param asc. */
+/* Global top-k record (24 B): ordered by sharpe desc, then sym asc, then param asc. Sharpe by its
+ * orderable bit pattern (+0.0 ranks above -0.0). sym is a symbol id, and symbol ids lie in
+ * [0, 2^31): there the device's unsigned tie-break and the host's signed compare are one order. */
 typedef struct bt_topk_rec {
     double sharpe;
     int32_t sym;
@@ -177,7 +179,10 @@ int32_t bt_last_batch_profile(bt_engine* e, bt_batch_profile* out);
 int32_t bt_load_synthetic(bt_engine* e, uint64_t seed, int64_t sym_begin, int32_t n_sym,
                           int32_t n_bars, int32_t freq);
 /* Upload host SoA bars: symbol s has bars[s] rows starting at row offset row_off[s] in h/l/c.
- * h and l may be NULL unless the strategy is BT_BOLL. */
+ * h and l may be NULL unless the strategy is BT_BOLL. Every sym_ids[s] must lie in [0, 2^31) (the
+ * range bt_load_synthetic generates; the engine keeps ids as int32 and orders ties by them): an id
+ * outside it is refused with its index and value named, before anything is laid out, so the
+ * dataset loaded before stays resident and the engine usable. */
 int32_t bt_load_ohlc(bt_engine* e, int32_t n_sym, const int64_t* sym_ids, const int32_t* bars,
                      const int64_t* row_off, const int32_t* h, const int32_t* l,
                      const int32_t* c);
@@ -262,6 +267,19 @@ int32_t bt_surface(bt_engine* e, bt_param_agg* agg, bt_topk_rec* best);
  * gives P empty aggregates and no best record; S < 0 or P < 1 is refused. */
 int32_t bt_surface_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum,
                       const int32_t* sym_ids, bt_param_agg* agg, bt_topk_rec* best);
+/* The run's top-k chain (k_topk.hip: radix select, then the sort or the tie finish in one block)
+ * on a caller's records: sum is a row-major S x P matrix, sym_ids[S] the rows' ids, and out[k]
+ * receives the min(k, S*P) best records in the order of bt_topk_rec, exactly what bt_read_topk
+ * would return after a run that left these summaries. lds_free_hist != 0 selects the histogram
+ * kernel without LDS (used up to 2^18 records, as in a run). Returns the number of records
+ * written. Synchronous like bt_replay: waits for the engine's streams, runs on the engine stream,
+ * copies back. Its whole work set is staged beside the records, so it works on any engine (also
+ * one created with topk = 0 and no dataset) and changes nothing another entry point reads. Added
+ * within ABI 3 (additive). Returns -1 with bt_last_error naming the offending value (the engine
+ * stays usable): a null engine, S < 1 or P < 1, S*P > 2^22, k outside [1, 1024], a NULL sum,
+ * sym_ids or out, an id below 0. */
+int32_t bt_topk_of(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum,
+                   const int32_t* sym_ids, int32_t k, int32_t lds_free_hist, bt_topk_rec* out);
 /* Symbol chunks the reduction is cut into: 0 = the planner's choice, n = always n (clipped to S).
  * Results are identical either way. */
 int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks);

@@ -11,7 +11,7 @@ the engine launches (bt_last_segments equals the planner's G for the device's CU
 import pytest
 
 import dbx_amd as D
-from helpers import launch_plan
+from helpers import assert_staging_layout, build_plan_driver, launch_plan, run_driver
 
 EMA_960 = lambda: D.Grid.ema_ols(list(range(3, 3 + 2 * 29, 2)) + [3000], list(range(4, 4 + 5 * 32, 5)),
                                  band_bps=15)   # test_gpu_segments.test_ema_split_many_param_blocks
@@ -87,3 +87,36 @@ def test_the_table_holds_the_shapes_it_is_there_for():
 def test_a_refused_grid_reports_the_engines_error():
     assert launch_plan(D.Grid.boll([8000], [2], [50], [50])) == {
         "error": "Bollinger grid needs more LDS than a CU has (windows too long)"}
+
+
+# ---- the staging of bt_topk_of (plan_topk_of, through tests/plan/topk_plan_driver.cpp)
+TOPK_SOURCES = ("plan.cpp", "topk_rules.cpp")
+
+
+def _check_topk_layout(pl, S, P):
+    """The uploads (keys, summaries, one descriptor per row) and a whole TopkWork of the call's
+    own: disjoint, 256-byte aligned, inside staging_bytes."""
+    n = S * P
+    assert (pl["summary_bytes"], pl["sym_bytes"], pl["rec_bytes"], pl["cap"], pl["kmax"]) == (48, 16, 24, 2048, 1024)
+    assert_staging_layout([(pl["o_key"], n * 8), (pl["o_sum"], n * 48), (pl["o_syms"], S * 16),
+                           (pl["o_hist"], 4096 * 4), (pl["o_state"], 4 * 8), (pl["o_counts"], 2 * 4),
+                           (pl["o_above"], 2048 * 8), (pl["o_cand"], 2048 * 8), (pl["o_out"], 1025 * 24)],
+                          pl["staging_bytes"], f"{S} x {P}")
+    assert pl["o_key"] == 0
+
+
+@pytest.mark.parametrize("S,P", [(1, 1), (2049, 1), (1, 2049), (3, 683), (1 << 22, 1), (1, 1 << 22), (2048, 2048),
+                                 (33, 70_001)])
+def test_plan_topk_of_lays_out_disjoint_aligned_regions(S, P):
+    exe = build_plan_driver("topk_plan_driver", TOPK_SOURCES)
+    pl = run_driver(exe, "plan", S, P)
+    assert pl == run_driver(exe, "plan", S, P), "the plan is a function of its arguments"
+    _check_topk_layout(pl, S, P)
+
+
+def test_plan_topk_of_under_asan_and_ubsan():
+    exe = build_plan_driver("topk_plan_driver", TOPK_SOURCES, sanitize=True)
+    for S, P in ((1, 1), (2049, 1), (1 << 22, 1)):
+        pl = run_driver(exe, "plan", S, P, sanitized=True)
+        _check_topk_layout(pl, S, P)
+        assert pl == run_driver(build_plan_driver("topk_plan_driver", TOPK_SOURCES), "plan", S, P)
