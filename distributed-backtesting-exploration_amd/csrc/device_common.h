@@ -7,7 +7,7 @@
 namespace bt {
 
 // Trade hash (spec §4): h = sum over trades of mix(w) mod 2^64, w = entry | exit << 31 |
-// (side > 0) << 62. A sum, so the hashes of consecutive bar segments add (k_tile.hip segments).
+// (side > 0) << 62. A sum, so the hashes of consecutive bar segments add (k_ema.hip, k_boll.hip segments).
 __host__ __device__ inline uint64_t trade_mix(uint64_t w) {
     const uint64_t z = (w ^ (w >> 29)) * 0xBF58476D1CE4E5B9ULL;
     return z ^ (z >> 32);

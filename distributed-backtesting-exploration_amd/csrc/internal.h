@@ -8,7 +8,7 @@
 #include "../../include/bt.h"
 
 // Profiling switches (phase ablation, s_memtime stamps, launch-shape overrides from the
-// environment) exist only in the profiling build (`make PROFILING=1` -> libbt_prof.so). In the
+// environment) exist only in the profiling build (`make PROFILING=1` -> dev/prof.so). In the
 // release libbt.so BT_ABL is the constant false: no environment variable can change a result.
 #ifdef BT_PROFILING
 #define BT_ABL(g, bit) (((g).ablate & (bit)) != 0)
@@ -72,7 +72,7 @@ struct Out {
     unsigned long long* dbg;       // profiling stamps (Grid::ablate & 64), else nullptr
 };
 
-// Bar-axis split of the tile kernels (k_tile.hip): each symbol's tiles are cut into G
+// Bar-axis split of the tile kernels (k_ema.hip, k_boll.hip): each symbol's tiles are cut into G
 // segments walked by separate workgroups. Segment s >= 1 starts flat `burn_tiles` tiles before
 // its first bar (a walk whose accounting is discarded) and records the state it reached there;
 // a fix pass per boundary re-walks a segment from the true state (the previous segment's end)

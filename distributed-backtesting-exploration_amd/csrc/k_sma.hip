@@ -29,6 +29,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "launch_run.h"
 #include "lds_layout.h"
 #include "plan.h"
 #include "tile_common.h"
@@ -102,13 +103,13 @@ __device__ __forceinline__ void stage_ring(int32_t c, int B, int t0, int lane, i
 
 // Stage 2 for one tile: int32 floor keys for every window. lane = bar, so the window length
 // and its reciprocal are wave-uniform and the top of the ring is read once per tile.
-// Windows are handed out dynamically, kKeyGrab per grab: every wave of the block (helper
-// included) grabs window groups from an LDS counter after its other work for the tile, so waves
-// with few flips to walk compute more keys. Round r owns counter values [r*per, (r+1)*per) with
-// per = kKeyGrab * (ceil(nw / kKeyGrab) + nwaves): the group grabs plus exactly one failing grab
-// per wave (the barrier separates rounds). The next group's atomic is in flight while the
-// current group computes (its result is read only at the end of the iteration), and the group's
-// ring reads are issued together.
+// Windows are handed out dynamically, kKeyGrab per grab (tile_common.h grab_issue): every wave
+// of the block (helper included) grabs window groups from an LDS counter after its other work
+// for the tile, so waves with few flips to walk compute more keys. Round r owns counter values
+// [r*per, (r+1)*per) with per = kKeyGrab * (ceil(nw / kKeyGrab) + nwaves): the group grabs plus
+// exactly one failing grab per wave (the barrier separates rounds). The next group's atomic is
+// in flight while the current group computes (its result is read only at the end of the
+// iteration), and the group's ring reads are issued together.
 // A group's four lengths and reciprocals come from the engine's tables in global memory
 // (Grid::kwin, Grid::krecip) at a wave-uniform index: scalar loads into SGPRs, issued as soon as
 // the group is known (the end of the previous iteration), so the wait at the top of the
@@ -118,11 +119,6 @@ __device__ __forceinline__ void stage_ring(int32_t c, int B, int t0, int lane, i
 // Bars without a full window (or past the series end) get key -1 on fast rows and -2 on slow
 // rows: their difference is never 0, so they never look like ties to the compare stage (they
 // are outside every lane's decision mask anyway).
-__device__ __forceinline__ uint32_t grab_issue(uint32_t* ctr, int lane) {
-    uint32_t v = 0;
-    if (lane == 0) v = atomicAdd(ctr, (uint32_t)kKeyGrab);
-    return v;
-}
 
 // floor(F / W) for the exact window sum F (an integer < 2^53 held as a double, F/W < 2^31):
 // one multiply by an UPWARD-biased reciprocal iw = RN(RN(1/W) * (1 + 2^-47)) and a truncating
@@ -181,11 +177,11 @@ __device__ __forceinline__ void stage_keys(int t0, int B, int nwp, int nf, int w
     // wave-uniform: every bar of the tile has a full window for every window length
     const bool full = t0 + 1 - wmax >= 0 && t0 + kTile <= B;
     const uint32_t base = round * key_round_len(nwp, nwaves);
-    uint32_t w = __builtin_amdgcn_readlane(grab_issue(ctr, lane), 0) - base;
+    uint32_t w = __builtin_amdgcn_readlane(grab_issue<kKeyGrab>(ctr, lane), 0) - base;
     KeyGroup gw = key_group(kwin, krecip, w, nwp);
 #pragma unroll 1
     while (w < (uint32_t)(nwp + kKeyGrab)) {
-        const uint32_t vn = grab_issue(ctr, lane);  // next group, read at the end
+        const uint32_t vn = grab_issue<kKeyGrab>(ctr, lane);  // next group, read at the end
         if (w == 0) {  // the table task (counter value 0 of the round)
             dst_build<true>(cTr[lane], lane, Dr);
             w = __builtin_amdgcn_readlane(vn, 0) - base;
@@ -823,7 +819,7 @@ __device__ __forceinline__ void sma_body(const SymDesc* __restrict__ syms,
         }
         return;
     }
-    if (active) {
+    if (active) {  // (tile_common.h write_summary, written out: through it sma_kernel's epilogue changes)
         const uint64_t s1lo = a.s1.lo, s2lo = a.s2.lo;
         const int64_t s1hi = a.s1.hi64(), s2hi = a.s2.hi64();
         const double sh = sharpe_fx(s1lo, s1hi, s2lo, s2hi, B, g.sqrt_ann);
@@ -925,21 +921,10 @@ __global__ __launch_bounds__(256) void sma_seg_combine(const SymDesc* __restrict
             }
         }
         if (i < n) {
+            // bars held: trades are back to back from the first entry to the forced exit at B-1
             const int B = syms[s].bars;
-            const uint64_t s1lo = (uint64_t)s1, s2lo = (uint64_t)s2;
-            const int64_t s1hi = (int64_t)(s1 >> 64), s2hi = (int64_t)(s2 >> 64);
-            const double sh = sharpe_fx(s1lo, s1hi, s2lo, s2hi, B, sqrt_ann);
-            bt_summary r;
-            r.n_trades = ntr;
-            r.status = 0;
-            r.pnl = R;
-            r.mdd = mdd;
-            r.exposure = ntr > 0 ? B - 1 - e0 : 0;
-            r.sharpe = sh;
-            r.hash = h;
-            out.sum[i] = r;
-            out.key[i] = order_key(sh);
-            if (out.sums != nullptr) out.sums[i] = bt_sums{s1lo, s1hi, s2lo, s2hi};
+            write_summary(out, i, ntr, R, mdd, ntr > 0 ? B - 1 - e0 : 0, h, (uint64_t)s1, (int64_t)(s1 >> 64),
+                          (uint64_t)s2, (int64_t)(s2 >> 64), B, sqrt_ann);
         }
     }
     wave_add_trades(out, ntr);
@@ -951,25 +936,17 @@ template <bool ONE_TRIP>
 hipError_t launch_sma_variant(const SymDesc* syms, int32_t n_sym, const int32_t* close,
                               const Grid& g, const Out& out, bool parity, const SegArgs& seg,
                               const LaunchPlan& pl, hipStream_t st) {
-    const dim3 grid(n_sym, pl.grid_y), block(pl.block);
-    if (pl.G > 1) {
-        // speculative segments, the fix pass of each boundary in order (a block returns at once
-        // when every lane started in the true position), then the fold
-        const dim3 sgrid(n_sym, pl.grid_y, pl.G), fgrid(n_sym, pl.grid_y, 1);
-        for (int s = 0; s < pl.G; ++s)
-            hipLaunchKernelGGL((sma_seg_kernel<ONE_TRIP>), s == 0 ? sgrid : fgrid, block, pl.lds, st, syms,
-                               close, g, out, pl.dedicated, seg, s);
-        const size_t n = (size_t)n_sym * g.n_params;
-        hipLaunchKernelGGL(sma_seg_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, syms, n_sym,
-                           g.n_params, reinterpret_cast<const SmaSegRec*>(seg.rec), pl.G, g.sqrt_ann, out);
-    } else if (parity) {
-        hipLaunchKernelGGL((sma_kernel<true, false, ONE_TRIP>), grid, block, pl.lds, st, syms, close, g, out,
-                           pl.dedicated);
-    } else {
-        hipLaunchKernelGGL((sma_kernel<false, false, ONE_TRIP>), grid, block, pl.lds, st, syms, close, g, out,
-                           pl.dedicated);
-    }
-    return hipGetLastError();
+    const dim3 block(pl.block);
+    auto kernel = [&](auto v, dim3 grid, int s) {
+        if constexpr (decltype(v)::value == Variant::kSeg)
+            hipLaunchKernelGGL((sma_seg_kernel<ONE_TRIP>), grid, block, pl.lds, st, syms, close, g, out,
+                               pl.dedicated, seg, s);
+        else
+            hipLaunchKernelGGL((sma_kernel<decltype(v)::value == Variant::kParity, false, ONE_TRIP>), grid, block,
+                               pl.lds, st, syms, close, g, out, pl.dedicated);
+    };
+    auto fold = [&] { enqueue_fold(sma_seg_combine, seg.rec, syms, n_sym, g, pl.G, out, st); };
+    return launch_run(kernel, fold, n_sym, parity, pl);
 }
 
 }  // namespace

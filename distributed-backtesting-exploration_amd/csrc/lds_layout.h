@@ -1,5 +1,5 @@
 // lds_layout.h — how the strategy kernels carve up their dynamic LDS, with the constants the
-// layouts use. Included by the kernels (k_sma.hip, k_tile.hip), which take their buffers from
+// layouts use. Included by the kernels (k_sma.hip, k_ema.hip, k_boll.hip), which take their buffers from
 // these offsets, and by the host planner (plan.cpp), which checks and requests the same totals.
 #pragma once
 #include "device_common.h"
@@ -32,7 +32,7 @@ __host__ __device__ inline SmaLds sma_lds_layout(int ring, int nw) {
     return L;
 }
 
-// ---------------------------------------------------- EMA+OLS and Bollinger (k_tile.hip)
+// ---------------------------------------------------- EMA+OLS and Bollinger (k_ema.hip, k_boll.hip)
 constexpr int kEStride = kTile + 1;  // ema buffer row stride (doubles): conflict-free columns
 // Bollinger tile buffers: scanned (k+2), flagged (k+1), walked (k) and accounted (k-1, by the
 // accountant wave of a split walk)

@@ -83,7 +83,7 @@ std::string plan_grid(const bt_config& c, Grid& g) {
             g.wmax = amax(1);
             // prefix ring, rounded up to a multiple of the tile: a window back from the stage being
             // flagged, which ends two 128-bar stages (four tiles) before the last scanned bar
-            // (k_tile.hip ema_tile_kernel)
+            // (k_ema.hip ema_tile_kernel)
             g.ring = (g.wmax + 5 * kTile - 1) / kTile * kTile;
             if (ema_lds_bytes(g, 1) > kCuLdsBytes) return "EMA grid needs more LDS than a CU has (OLS windows too long)";
             break;
@@ -95,7 +95,7 @@ std::string plan_grid(const bt_config& c, Grid& g) {
             // w * max(k_num, k_den) < 2^32 (spec §4, oracle/oracle.c orc_boll)
             const int64_t kmax = std::max<int64_t>(c.k_den, amax(1));
             if ((int64_t)g.wmax * kmax >= (1LL << 32)) return "Bollinger grid outside the exact int128 range (window * k >= 2^32)";
-            // prefix rings: the longest window + three tiles in flight (k_tile.hip: scanned k+2,
+            // prefix rings: the longest window + three tiles in flight (k_ema.hip, k_boll.hip: scanned k+2,
             // flagged k+1, walked k), rounded up to a multiple of the tile
             g.ring = (g.wmax + 4 * kTile - 1) / kTile * kTile;
             for (int q = 0; q < 8; ++q) {
@@ -226,7 +226,7 @@ int tile_lanes_per_wave() {
     return l;
 }
 
-// Hardware wave -> role of a Bollinger block (k_tile boll_tile_kernel wave_map). Hardware wave w
+// Hardware wave -> role of a Bollinger block (k_boll.hip boll_tile_kernel wave_map). Hardware wave w
 // runs on SIMD w % 4, so waves w and w + 4 share one: each busy parameter wave (the walks, the
 // busiest first) gets a task-only wave as its partner (task waves take fewer tasks when their
 // SIMD is busy), the lightest parameter wave the helper, and the accountant of a split walk a

@@ -1,7 +1,7 @@
 // plan.h — everything the host decides before a launch, as pure functions of the configuration,
 // the dataset shape and a CU count (plan.cpp). No HIP call, no device state: the engine
 // (engine.cpp, analysis.cpp) asks for a plan and sizes its buffers from it, the launchers
-// (k_sma.hip, k_tile.hip) enqueue what it says, and tests/plan/*_driver.cpp print it without a GPU.
+// (k_sma.hip, k_ema.hip, k_boll.hip) enqueue what it says, and tests/plan/*_driver.cpp print it without a GPU.
 // The plan of an analysis call (replay, surface, walk-forward) also owns the layout of the call's
 // device staging: the engine allocates staging_bytes, never fewer than 256 for a call it does not
 // refuse, and every region the plan names lies inside them.

@@ -1,10 +1,64 @@
-// tile_common.h — pieces shared by the tile-pipelined strategy kernels (k_tile.hip):
-// the per-tile close scan (returns, drawdown sparse table) and the per-lane trade accounting
-// that runs only at position changes. Spec: docs/oracle_spec.md §3-§4.
+// tile_common.h — pieces shared by the tile-pipelined strategy kernels (k_ema.hip, k_boll.hip;
+// the task grab and the folds' result write by k_sma.hip too): small wave helpers, the
+// per-tile close scan (returns, drawdown sparse table) and the per-lane trade accounting that
+// runs only at position changes. Spec: docs/oracle_spec.md §3-§4.
 #pragma once
 #include "device_common.h"
 
 namespace bt {
+
+__device__ __forceinline__ int32_t ldc(const int32_t* __restrict__ row, int B, int t, int32_t pad) {
+    return t < B ? row[t] : pad;
+}
+
+// Task counter in LDS: a wave's lane 0 takes INC counter values. Tile kernels: round r owns
+// counter values [r * (n + nwaves), (r + 1) * (n + nwaves)): n successful grabs plus exactly one
+// failing grab per wave (the barrier separates rounds); k_sma.hip stage_keys takes kKeyGrab at a
+// time. grab_issue returns the atomic's VGPR; the caller reads lane 0 only when it needs the
+// value, so the next grab's round trip overlaps the current task.
+template <uint32_t INC = 1>
+__device__ __forceinline__ uint32_t grab_issue(uint32_t* ctr, int lane) {
+    uint32_t v = 0;
+    if (lane == 0) v = atomicAdd(ctr, INC);
+    return v;
+}
+__device__ __forceinline__ uint32_t grab_value(uint32_t v) { return __builtin_amdgcn_readlane(v, 0); }
+
+// Prefix rings: entry x (the sum over bars < x) lives at x mod R, with R a multiple of 64 of at
+// least the longest window + 3 tiles (plan.cpp plan_grid), so windows up to the spec's 4,096 bars fit
+// in LDS. Position of x = T*64 + lane + 1, and of x - W given that position (0 < W < R).
+__device__ __forceinline__ int ring_pos(int T, int lane, int R) {
+    const int p = (T % (R / kTile)) * kTile + lane + 1;
+    return p == R ? 0 : p;
+}
+__device__ __forceinline__ int ring_back(int p, int W, int R) {
+    const int q = p - W;
+    return q < 0 ? q + R : q;
+}
+
+// Lane mask of a condition (the builtin on the bool itself: HIP's __ballot(int) materialises the
+// condition in a VGPR and compares it again).
+__device__ __forceinline__ uint64_t ballot(bool c) { return __builtin_amdgcn_ballot_w64(c); }
+
+// Lane mask of w <= x (int32, w wave-uniform) straight from the compare's scalar destination (a
+// ballot of a bool that is not itself a compare costs two VALU more: the bool is materialised in
+// a VGPR and compared again).
+__device__ __forceinline__ uint64_t vcmp_le_i32(int32_t w, int32_t x) {
+    uint64_t m;
+    asm volatile("v_cmp_le_i32_e64 %0, %1, %2" : "=s"(m) : "s"(w), "v"(x));
+    return m;
+}
+
+// profiling stamps: the hardware placement (SE / CU / SIMD, XCD) of wave hw_wave < 8 of the
+// first kDbgBlocks blocks (internal.h)
+__device__ __forceinline__ void stamp_place(unsigned long long* dbg, int hw_wave, int lane) {
+    if (dbg == nullptr || lane != 0 || hw_wave >= 8 || blockIdx.x >= (unsigned)kDbgBlocks || blockIdx.y != 0 ||
+        blockIdx.z != 0)
+        return;
+    const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
+    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // XCC_ID
+    dbg[kDbgSlots + blockIdx.x * 8 + hw_wave] = ((unsigned long long)xcc << 32 | hw) | (1ull << 40);
+}
 
 // s_setprio takes an immediate: a wave-uniform priority through a scalar switch (folds to one
 // instruction for a constant)
@@ -274,6 +328,27 @@ __device__ __forceinline__ void acct_tile_end(TradeAcct& a, const Agg* D, const 
     a.ps1 = a.ps2 = 0;
 }
 
+// The result write of one (symbol, param), index i of the run's outputs: the Sharpe ratio from
+// the fixed-point sums, the summary, the order key and (parity mode) the sums themselves.
+__device__ __forceinline__ void write_summary(const Out& out, size_t i, int32_t ntr, int64_t pnl,
+                                              int64_t mdd, int64_t expo, uint64_t hash, uint64_t s1lo,
+                                              int64_t s1hi, uint64_t s2lo, int64_t s2hi, int bars,
+                                              double sqrt_ann) {
+    const double sh = sharpe_fx(s1lo, s1hi, s2lo, s2hi, bars, sqrt_ann);
+    bt_summary r;
+    r.n_trades = ntr;
+    r.status = 0;
+    r.pnl = pnl;
+    r.mdd = mdd;
+    r.exposure = expo;
+    r.sharpe = sh;
+    r.hash = hash;
+    out.sum[i] = r;
+    out.key[i] = order_key(sh);
+    if (out.sums != nullptr) out.sums[i] = bt_sums{s1lo, s1hi, s2lo, s2hi};
+}
+
+// (write_summary, kept written out: through the helper the unsplit EMA kernels' epilogue changes)
 __device__ __forceinline__ void acct_write(const TradeAcct& a, int bars, double sqrt_ann,
                                            size_t gi, const Out& out) {
     const uint64_t s1lo = a.s1.lo64(), s2lo = a.s2.lo64();
@@ -382,31 +457,35 @@ __device__ __forceinline__ void seg_write_rest(const TradeAcct& a, SegRec* mine)
     for (int i = 0; i < 7; ++i) dst[i] = src[i];
 }
 
-__device__ __forceinline__ void seg_write(const TradeAcct& a, int start_pos, int start_e, SegRec* mine) {
-    SegRec r;
-    r.ntr = a.ntr;
-    r.expo = a.expo;
-    r.start_pos = start_pos;
-    r.start_e = start_e;
-    r.end_pos = a.pos;
-    r.end_e = a.e;
-    r.end_ce = a.ce;
-    r.pad = 0;
-    r.end_agg[0] = a.agg.mx;
-    r.end_agg[1] = a.agg.mn;
-    r.end_agg[2] = a.agg.dd;
-    r.end_agg[3] = a.agg.du;
-    r.R = a.R;
-    r.A = -a.R;
-    r.B = a.Bq;
-    r.C = a.C;
-    r.D = a.D;
-    r.h = a.h;
-    r.s1lo = a.s1.lo64();
-    r.s1hi = a.s1.hi64();
-    r.s2lo = a.s2.lo64();
-    r.s2hi = a.s2.hi64();
-    *mine = r;
+// Body of a tile kernel's fold kernel (ema_seg_combine, boll_seg_combine; 256 lanes per block, one
+// per (symbol, param)): folds the bar segments in order: additive counts, pnl, hash and return
+// sums; the drawdown forms composed from g = m = 0 (TradeAcct).
+__device__ __forceinline__ void seg_fold(const SymDesc* __restrict__ syms, int n_sym, int P,
+                                         const SegRec* __restrict__ rec, int G, double sqrt_ann,
+                                         const Out& out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = (size_t)n_sym * P;
+    int ntr = 0;
+    if (i < n) {
+        const int s = (int)(i / P);
+        int64_t expo = 0, R = 0, gap = 0, mdd = 0;
+        uint64_t h = 0;
+        i128 s1 = 0, s2 = 0;
+        for (int q = 0; q < G; ++q) {
+            const SegRec& r = rec[(size_t)q * n + i];
+            ntr += r.ntr;
+            expo += r.expo;
+            R += r.R;
+            h += r.h;
+            s1 += (i128)(((unsigned __int128)(uint64_t)r.s1hi << 64) | r.s1lo);
+            s2 += (i128)(((unsigned __int128)(uint64_t)r.s2hi << 64) | r.s2lo);
+            mdd = max(mdd, max(gap + r.C, r.D));
+            gap = max(gap + r.A, r.B);
+        }
+        write_summary(out, i, ntr, R, mdd, expo, h, (uint64_t)s1, (int64_t)(s1 >> 64), (uint64_t)s2,
+                      (int64_t)(s2 >> 64), syms[s].bars, sqrt_ann);
+    }
+    wave_add_trades(out, ntr);
 }
 
 // Diagnostic s_memtime stamps (Grid::ablate & 64 builds only): per role (0 = parameter waves,

@@ -1,7 +1,7 @@
 // walk_tile.h — one 64-bar tile of one (symbol, parameter) lane walked by one wave64, lane = bar:
 // the body shared by the lane kernels (k_replay.hip replay_kernel, k_walkfwd.hip wf_walk_kernel).
 // A device implementation of docs/oracle_spec.md §4/§5 beside the sweep kernels (k_sma.hip,
-// k_tile.hip).
+// k_ema.hip, k_boll.hip).
 //
 // Per tile, data-parallel: coalesced loads of c (h, l for Bollinger) and of the bar that leaves
 // each window (a second coalesced stream at t - w), window sums advanced by wave scans of

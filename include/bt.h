@@ -137,7 +137,7 @@ void bt_engine_destroy(bt_engine* e);
 const char* bt_last_error(void);      /* thread-local message of the last failed call */
 int32_t bt_abi_version(void);
 int32_t bt_num_params(const bt_engine* e);
-/* Bar-axis split of every strategy's walk (k_tile.hip, k_sma.hip): segments per symbol (0 =
+/* Bar-axis split of every strategy's walk (k_ema.hip, k_boll.hip, k_sma.hip): segments per symbol (0 =
  * automatic: EMA+OLS and Bollinger split a shard with no more workgroups than the GPU has CUs, SMA
  * a shard of one-block-per-CU symbols that fills the GPU fewer than 16 times; 1 = never; n =
  * always n) and the burn-in tiles a speculative segment walks before its first bar (0 = the

@@ -21,6 +21,7 @@ for l in text:
     m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
     if m:
         files[int(m.group(1))] = (m.group(3) or m.group(2)).split("/")[-1]
+kfile = next((f for f in files.values() if f.endswith(".hip")), "?")  # the listing's kernel file
 start = next(i for i, l in enumerate(text) if re.match(r"^_Z\w*:", l) and want in l)
 end = next(i for i in range(start + 1, len(text)) if text[i].startswith(".Lfunc_end"))
 
@@ -179,10 +180,10 @@ for h in sorted(loops, key=lambda x: blocks[x]["line"] or 0):
         for op, _, lc in blocks[b]["ins"]:
             if klass(op) in ("valu", "xlane"):
                 src[lc] += 1
-    kt = sorted(n for (f, n) in src if f == "k_tile.hip" and n > 0)
+    kt = sorted(n for (f, n) in src if f == kfile and n > 0)
     print(f"loop @{blocks[h]['line']} ({len(body)} blocks, listing {lines[0]}-{lines[-1]}, "
           f"{len(inner)} inner): all {census(body)}  own {census(own)}  "
-          f"k_tile.hip {kt[0] if kt else '-'}-{kt[-1] if kt else '-'}")
+          f"{kfile} {kt[0] if kt else '-'}-{kt[-1] if kt else '-'}")
     if show_lines:
         for (f, n), c in sorted(src.items(), key=lambda x: (-x[1], x[0])):
             print(f"      {c:4d} valu  {f}:{n}")

@@ -28,7 +28,7 @@ kname = line["roofline"]["kernel"].split("::")[-1]
 steps = line["steps"]
 
 # One step launches the strategy kernel once, or, for a bar-split run, the speculative pass,
-# one fix pass per boundary and the combine pass (k_tile.hip): a step's kernel time is the sum
+# one fix pass per boundary and the combine pass (k_ema.hip, k_boll.hip): a step's kernel time is the sum
 # of its group of dispatches, the same span the bench line's HIP events bracket.
 def ours(name):
     # SMA bar segments launch sma_seg_kernel (speculative + fix passes) and sma_seg_combine

@@ -1,4 +1,4 @@
-"""CPU model of the EMA+OLS walk's latched positions (k_tile.hip ema_tile_kernel: `latch64` and
+"""CPU model of the EMA+OLS walk's latched positions (k_ema.hip ema_tile_kernel: `latch64` and
 the coupling fixpoint) against the sequential flat / long / short machine of
 docs/oracle_spec.md, on random 64-bar tiles whose condition words obey the nesting the kernel
 relies on (entry-long A and exit-long X disjoint, B and Y disjoint, A implies Y, B implies X),

@@ -8,7 +8,7 @@ A. |ret| = 1 on almost every bar (doubling cycles 1, 2, ..., 2^30): q2 = 2^56, s
    the wide branch of internal.h i128_to_double on the device) and the SMA kernel's uint64
    return partials come within 2^30 of 2^63 over a 128-bar pair (k_sma.hip).
 B. Bollinger z tests that are exactly tied, D^2 k_den^2 = k_num^2 Q with D != 0, or one tick
-   from tied, at operands up to 2^112: the fp64 bracket of k_tile.hip cannot decide them and
+   from tied, at operands up to 2^112: the fp64 bracket of k_boll.hip cannot decide them and
    the int128 settle path does, also in the second pass of 8 thresholds and at the edge of
    window * k < 2^32.
 C. One symbol of kMaxBars = 2^22 bars at prices within 2^21 of 2^31: the prefix of c ends
@@ -282,7 +282,7 @@ def _b_case(name):
 
 
 def _bracket(c, w, k_num, k_den):
-    """The fp64 z test of k_tile.hip (boll flags, `S2d` ... `ztest`), the same operations in the
+    """The fp64 z test of k_boll.hip (boll flags, `S2d` ... `ztest`), the same operations in the
     same order in numpy float64, for every full window of `c`; then the exact integers of the
     windows it leaves undecided. Returns per undecided window with D != 0 the pair (L, R) =
     (D^2 k_den^2, k_num^2 Q) as Python ints, and max(L, R) over all windows."""

@@ -231,7 +231,7 @@ def test_ema_series_cross_the_narrow_bound_after_warm_up():
 @pytest.mark.parametrize("parity", [False, True])
 def test_ema_narrow_to_wide_accounts_match_oracle(parity):
     """The EMA+OLS walk keeps gap and mdd in int32 while the closes' total variation is below
-    2^30 (k_tile.hip kEmaNarrow; fills are at closes, so the closes' TV bounds them), unsplit
+    2^30 (k_ema.hip kEmaNarrow; fills are at closes, so the closes' TV bounds them), unsplit
     runs only: every field and trade vs the C oracle across the crossing tiles."""
     grid = D.config3_grid()
     closes = _ema_series()

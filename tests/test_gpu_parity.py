@@ -458,7 +458,7 @@ def test_release_library_ignores_ablate_env(monkeypatch):
 
 def test_boll_many_k_values():
     """Bollinger grids with more than 8 z thresholds per window (condition words in passes of
-    8 k values, k_tile.hip): 12 k values x 3 windows, bit-exact trades vs the oracle."""
+    8 k values, k_boll.hip): 12 k values x 3 windows, bit-exact trades vs the oracle."""
     grid = D.Grid.boll([5, 20, 90], list(range(1, 13)), [50], [100], k_den=4)
     bars = 4000
     o, h, lo, c = _gen(0x5EED, [21, 22], bars, 1)

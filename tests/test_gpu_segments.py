@@ -1,4 +1,4 @@
-"""Bar-axis split of the Bollinger walk (k_tile.hip SEG; include/bt.h bt_set_segments): every
+"""Bar-axis split of the Bollinger walk (k_boll.hip SEG; include/bt.h bt_set_segments): every
 summary field of a split run must equal the unsplit run and the C oracle bit for bit, whatever
 the segment count and burn-in — including burn-ins too short for the speculative walk to meet
 the true one (the fix pass re-walks those boundaries) and segments with no bars at all."""

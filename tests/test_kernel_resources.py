@@ -25,40 +25,53 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
-def _kernels():
+def _code_objects(d):
+    """The gfx950 code objects bundled in LIB, unbundled into directory d (scripts/dev/kernel_res.py
+    reads them too)."""
     tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
     if not all(os.path.exists(t) for t in tools) or not os.path.exists(LIB):
         pytest.skip("ROCm LLVM tools or libbt.so missing")
-    objcopy, bundler, readelf = tools
+    objcopy, bundler, _ = tools
+    fat = os.path.join(d, "fat.bin")
+    subprocess.run([objcopy, "--dump-section", f".hip_fatbin={fat}", LIB], check=True)
+    data = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)]
+    for i, s in enumerate(starts):
+        part = os.path.join(d, f"b{i}.bin")
+        open(part, "wb").write(data[s:starts[i + 1] if i + 1 < len(starts) else len(data)])
+        co = os.path.join(d, f"co{i}.o")
+        r = subprocess.run([bundler, "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                            f"--input={part}", f"--output={co}"], capture_output=True)
+        if r.returncode == 0 and os.path.exists(co) and os.path.getsize(co) > 0:
+            yield co
+
+
+_META = (".private_segment_fixed_size", ".vgpr_count", ".sgpr_count", ".vgpr_spill_count")
+
+
+def _kernels():
     out = {}
-    objdump = os.path.join(LLVM, "llvm-objdump")
+    readelf, objdump = os.path.join(LLVM, "llvm-readelf"), os.path.join(LLVM, "llvm-objdump")
     with tempfile.TemporaryDirectory() as d:
-        fat = os.path.join(d, "fat.bin")
-        subprocess.run([objcopy, "--dump-section", f".hip_fatbin={fat}", LIB], check=True)
-        data = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)]
-        for i, s in enumerate(starts):
-            part = os.path.join(d, f"b{i}.bin")
-            open(part, "wb").write(data[s:starts[i + 1] if i + 1 < len(starts) else len(data)])
-            co = os.path.join(d, f"co{i}.o")
-            r = subprocess.run([bundler, "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                                f"--input={part}", f"--output={co}"], capture_output=True)
-            if r.returncode != 0 or not os.path.exists(co) or os.path.getsize(co) == 0:
-                continue
+        for co in _code_objects(d):
             notes = subprocess.run([readelf, "--notes", co], capture_output=True, text=True).stdout
             if os.path.exists(objdump):
                 dis = subprocess.run([objdump, "-d", "--mcpu=gfx950", co], capture_output=True, text=True).stdout
                 for fname, hot in _scratch_in_loops(dis).items():
                     out.setdefault(fname, {})["scratch_in_loops"] = hot
-            name = None
+            name, lds = None, None  # a kernel's keys are sorted: its LDS size precedes its name
             for line in notes.splitlines():
                 line = line.strip()
                 if line.startswith(".name:"):
                     name = line.split(":", 1)[1].strip()
                     out.setdefault(name, {})
+                    if lds is not None:
+                        out[name]["group_segment_fixed_size"], lds = lds, None
+                elif line.startswith(".group_segment_fixed_size:"):
+                    lds = int(line.split(":", 1)[1])
                 elif name and ":" in line:
                     k, v = line.split(":", 1)
-                    if k in (".private_segment_fixed_size", ".vgpr_count", ".vgpr_spill_count"):
+                    if k in _META:
                         out[name][k[1:]] = int(v)
     if not out:
         pytest.skip("no gfx950 code objects found in libbt.so")

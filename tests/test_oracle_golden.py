@@ -160,7 +160,7 @@ def test_numpy_restatement_matches_c_fresh():
 
 
 def test_sltp_level_floor():
-    """k_tile.hip level_y: trunc(fl(ce * fl(f * fl(1e-4))) + 2^-16) == floor(ce * f / 10000) (the
+    """k_boll.hip level_y: trunc(fl(ce * fl(f * fl(1e-4))) + 2^-16) == floor(ce * f / 10000) (the
     oracle's integer SL/TP levels, oracle/oracle.c orc_boll) for every factor f = 10000 -+ bps,
     bps in [0, 9999], at random prices and at prices whose product leaves remainder 0, 1 or 9999
     (the only places a rounding error could move the truncation) near 2^31."""

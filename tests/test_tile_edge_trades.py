@@ -3,7 +3,7 @@ with a position carried in from earlier tiles; later trades of the tile open ins
 parity cases must hold both shapes often:
 
 * a carried Bollinger position filled by SL/TP on the FIRST bar of a tile (the one fill whose
-  path before the fill bar is empty in this tile: `k_tile.hip` boll walk, `qi < a.sb`);
+  path before the fill bar is empty in this tile: `k_boll.hip` boll walk, `qi < a.sb`);
 * a carried position closed in a tile and further trades (or reversals) after it in the same
   tile (the non-first, merge-free walk iterations).
 
@@ -40,7 +40,7 @@ def _case(seed):
 GRIDS = {
     "boll": lambda: D.Grid.boll([4, 9, 30], [1, 2, 4], [5, 25], [5, 40], k_den=2),
     # more than one parameter wave: the launcher splits the walk of the busiest wave into a
-    # finder and an accountant (k_tile.hip), so these shapes run through the trade records
+    # finder and an accountant (k_boll.hip), so these shapes run through the trade records
     "boll_split": lambda: D.Grid.boll([4, 9, 30, 60], [1, 2, 4], [5, 25], [5, 40, 80], k_den=2),
     "ema_ols": lambda: D.Grid.ema_ols([3, 8, 40], [4, 16], band_bps=0),
     # 128-bar stages: the 1,560-bar window's prefix ring makes 64-bar stages no denser in LDS
