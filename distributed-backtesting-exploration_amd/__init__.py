@@ -12,12 +12,14 @@ from .engine import (ABI_VERSION, FOLD_DTYPE, PIPE_SLOTS, WALKFWD_FOLDS_MAX, WF_
                      BT_SMA_CROSS, LANE_DTYPE, PARAM_AGG_DTYPE, REPLAY_MAX, SUMMARY_DTYPE, SURFACE_OF_MAX,
                      TOPK_DTYPE, TOPK_OF_MAX, TRADE_DTYPE, BtError, Engine, Grid, Replay, Surface, as_lanes, build,
                      config2_grid, config3_grid, config4_grid, config5_grid, lib, merge_surfaces,
-                     merge_topk, surface_host)
+                     merge_topk, surface_host, PF_LANE_DTYPE, PF_SUMMARY_DTYPE, PORTFOLIO_MAX, Portfolio, as_pf_lanes,
+                     merge_portfolios, portfolio_host, walk_forward_lanes)
 
 __all__ = [
     "ABI_VERSION", "FOLD_DTYPE", "PIPE_SLOTS", "WALKFWD_FOLDS_MAX", "WF_STEP_DTYPE", "WalkForward", "walk_forward_host", "BT_BOLL", "BT_DAILY", "BT_EMA_OLS", "BT_FLAG_PARITY", "BT_FLAG_TIMING", "BT_MINUTE",
     "BT_SMA_CROSS", "LANE_DTYPE", "PARAM_AGG_DTYPE", "REPLAY_MAX", "SUMMARY_DTYPE", "SURFACE_OF_MAX",
     "TOPK_DTYPE", "TOPK_OF_MAX", "TRADE_DTYPE", "BtError", "Engine", "Grid", "Replay", "Surface", "as_lanes", "build",
     "config2_grid", "config3_grid", "config4_grid", "config5_grid", "lib", "merge_surfaces",
-    "merge_topk", "surface_host",
+    "merge_topk", "surface_host", "PF_LANE_DTYPE", "PF_SUMMARY_DTYPE", "PORTFOLIO_MAX", "Portfolio", "as_pf_lanes",
+    "merge_portfolios", "portfolio_host", "walk_forward_lanes",
 ]

@@ -1,6 +1,6 @@
-// analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of, bt_topk_of
-// and bt_walk_forward with their two settings. Each call checks its arguments with the pure rules of
-// replay.h / surface.h / topk_rules.h / walkfwd.h, asks plan.h for its chunks and its staging
+// analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of, bt_topk_of,
+// bt_walk_forward and bt_portfolio with their settings. Each call checks its arguments with the pure rules
+// of replay.h / surface.h / topk_rules.h / walkfwd.h / portfolio.h, asks plan.h for its chunks and its staging
 // layout, realises that layout in the engine's one arena (engine_state.h), launches, and copies the
 // results back before it returns. Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "engine_state.h"
+#include "portfolio.h"
 #include "replay.h"
 #include "surface.h"
 #include "topk_rules.h"
@@ -246,9 +247,69 @@ int32_t walk_forward_impl(bt_engine* e, int32_t K, const int32_t* bounds, int32_
     return 0;
 }
 
+// ---- bt_portfolio: chosen lanes traded together, per bar (k_portfolio.hip)
+// The entries with a non-empty window go up once, the accumulators are zeroed, the walk adds into
+// them and the finish writes the four rows and the summary, which one copy brings back.
+int32_t portfolio_impl(bt_engine* e, int32_t n, const bt_pf_lane* lanes, int32_t T, int64_t* pnl, int64_t* equity,
+                       int32_t* n_long, int32_t* n_short, bt_pf_summary* summary) {
+    const char* fn = "bt_portfolio";
+    if (!e) refuse(fn, "null engine");
+    std::string why = portfolio_refusal(!e->syms.empty(), n, lanes != nullptr, T,
+                                        pnl || equity || n_long || n_short || summary);
+    if (!why.empty()) refuse(fn, why);
+    PfResolved rs;
+    why = portfolio_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, T, rs);
+    if (!why.empty()) refuse(fn, why);
+    const int32_t m = (int32_t)rs.req.size();
+    const PortfolioPlan pl = plan_portfolio(m, T, e->cus, e->portfolio_replicas);
+    uint8_t* base = enter(e, pl.staging_bytes);
+    e->h_portfolio.ensure(pl.out_bytes);
+    PfLane* d_lanes = at<PfLane>(base, pl.o_lanes);
+    PfWork w{};
+    w.acc_pnl = at<unsigned long long>(base, pl.o_acc_pnl);
+    w.acc_cnt = at<unsigned long long>(base, pl.o_acc_cnt);
+    w.pitch = pl.pitch;
+    w.R = pl.R;
+    w.T = T;
+    w.n_lanes = rs.n_lanes, w.lo = rs.lo, w.hi = rs.hi;
+    w.pnl = at<int64_t>(base, pl.o_pnl);
+    w.equity = at<int64_t>(base, pl.o_equity);
+    w.n_long = at<int32_t>(base, pl.o_long);
+    w.n_short = at<int32_t>(base, pl.o_short);
+    w.sum = at<bt_pf_summary>(base, pl.o_sum);
+    if (m > 0)
+        HIPCHK(hipMemcpyAsync(d_lanes, rs.req.data(), (size_t)m * sizeof(PfLane), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(base + pl.o_acc_pnl, 0, pl.acc_bytes, e->stream));
+    HIPCHK(launch_portfolio(d_lanes, m, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, w, pl, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_portfolio.p, base + pl.o_pnl, pl.out_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const uint8_t* h = e->h_portfolio.p;
+    const size_t bars = (size_t)T;
+    if (pnl) memcpy(pnl, h, bars * 8);
+    if (equity) memcpy(equity, h + (pl.o_equity - pl.o_pnl), bars * 8);
+    if (n_long) memcpy(n_long, h + (pl.o_long - pl.o_pnl), bars * 4);
+    if (n_short) memcpy(n_short, h + (pl.o_short - pl.o_pnl), bars * 4);
+    if (summary) memcpy(summary, h + (pl.o_sum - pl.o_pnl), sizeof *summary);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t bt_portfolio(bt_engine* e, int32_t n, const bt_pf_lane* lanes, int32_t T, int64_t* pnl, int64_t* equity,
+                     int32_t* n_long, int32_t* n_short, bt_pf_summary* summary) {
+    ABI_GUARD(-1, { return portfolio_impl(e, n, lanes, T, pnl, equity, n_long, n_short, summary); })
+}
+
+int32_t bt_set_portfolio_replicas(bt_engine* e, int32_t r) {
+    ABI_GUARD(-1, {
+        if (!e) refuse("bt_set_portfolio_replicas", "null engine");
+        if (r < 0) refuse("bt_set_portfolio_replicas", "r = " + std::to_string(r) + " is negative");
+        e->portfolio_replicas = r;
+        return 0;
+    })
+}
 
 int32_t bt_replay(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
                   int32_t* n_bars, bt_trade* trades, int64_t* equity, int8_t* pos, int64_t stride) {

@@ -182,6 +182,36 @@ hipError_t launch_wf_walk(const WfArgs& a, const int32_t* high, const int32_t* l
                           const Grid& g, hipStream_t st);
 hipError_t launch_wf_select(const WfArgs& a, const Grid& g, const WalkfwdPlan& pl, hipStream_t st);
 
+// Portfolio of chosen lanes (k_portfolio.hip, bt_portfolio; docs/portfolio_spec.md). The walk (one
+// wave64 workgroup per entry) adds every entry's per-bar pnl and position into replicated per-bar
+// accumulators with integer atomics; the finish (one block) folds the replicas into the output
+// rows, scans the equity and writes the summary. The host passes only entries whose clipped
+// window [from, to) is not empty, to <= min(bars, T), and zeroes the accumulators before the walk.
+struct PfLane {
+    int64_t off;                   // SymDesc::off of the entry's symbol
+    int32_t bars;
+    int32_t param;
+    int32_t from, to;              // the clipped window
+};
+static_assert(sizeof(PfLane) == 24, "PfLane layout");
+struct PfWork {
+    unsigned long long* acc_pnl;   // [R][pitch] sums of E_t - E_(t-1)
+    unsigned long long* acc_cnt;   // [R][pitch] n_long | n_short << 32
+    int64_t pitch;                 // elements per accumulator row: T rounded up to a tile
+    int32_t R;                     // replicas: workgroup b adds to replica b % R
+    int32_t T;                     // bars of the output rows
+    int32_t n_lanes, lo, hi;       // of the summary: entries, first bar, one past the last bar
+    int64_t* pnl;                  // [T] outputs
+    int64_t* equity;
+    int32_t* n_long;
+    int32_t* n_short;
+    bt_pf_summary* sum;
+};
+struct PortfolioPlan;
+hipError_t launch_portfolio(const PfLane* lanes, int32_t n, const int32_t* high, const int32_t* low,
+                            const int32_t* close, const Grid& g, const PfWork& w, const PortfolioPlan& pl,
+                            hipStream_t st);
+
 // Reductions of an S x P summary matrix (k_surface.hip, bt_surface / bt_surface_of): one pass over
 // the records writes per-chunk column aggregates and per-tile row winners, two short kernels fold
 // them into agg[P] and best[S]. Symbol s has id ids[s * id_stride] (the engine's SymDesc array or
@@ -296,6 +326,18 @@ __host__ __device__ inline double sharpe_fx(uint64_t s1lo, int64_t s1hi, uint64_
     const double m = ldexp(i128_to_double(s1lo, s1hi), -56) / n;
     const double mm = m * m;
     const double v = ldexp(i128_to_double(s2lo, s2hi), -56) / n - mm;
+    return v > 0 ? (m / sqrt(v)) * sqrt_ann : 0.0;
+}
+
+// Sharpe of a portfolio's per-bar tick increments (docs/portfolio_spec.md §4): the oracle's
+// formula on s1 = sum pnl[t], s2 = sum pnl[t]^2 over the n bars [lo, hi); 0 when there is none.
+__host__ __device__ inline double sharpe_ticks(uint64_t s1lo, int64_t s1hi, uint64_t s2lo,
+                                               int64_t s2hi, int32_t n_bars, double sqrt_ann) {
+    if (n_bars < 1) return 0.0;
+    const double n = (double)n_bars;
+    const double m = i128_to_double(s1lo, s1hi) / n;
+    const double mm = m * m;
+    const double v = i128_to_double(s2lo, s2hi) / n - mm;
     return v > 0 ? (m / sqrt(v)) * sqrt_ann : 0.0;
 }
 

@@ -460,6 +460,40 @@ WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int 
     return pl;
 }
 
+// ------------------------------------------------------------------------ portfolio of lanes
+PortfolioPlan plan_portfolio(int32_t n, int32_t T, int cus, int32_t replicas_req, size_t budget_req) {
+    PortfolioPlan pl{};
+    n = std::max(n, 0);
+    T = std::max(T, 1);
+    const size_t budget = budget_req > 0 ? budget_req : kPortfolioAccBudget;
+    pl.tiles = (T + kTile - 1) / kTile;
+    pl.pitch = (int64_t)pl.tiles * kTile;
+    const size_t row = (size_t)pl.pitch * 16;  // one replica of both accumulators
+    int32_t R = 1;
+    if (replicas_req > 0) {
+        R = std::min(replicas_req, kPortfolioMaxReplicas);
+        while (R > 1 && (size_t)R * row > budget) R /= 2;
+    } else {
+        while (R * 2 <= kPortfolioMaxReplicas && R * 2 <= n && (size_t)(R * 2) * row <= budget) R *= 2;
+    }
+    pl.R = R;
+    pl.finish_block = (int32_t)std::min<int64_t>(pl.pitch, 1024);
+    pl.fill = (double)n / ((double)std::max(cus, 1) * 4 * 8);
+    Carve c;
+    pl.o_lanes = c.take((size_t)n * sizeof(PfLane));
+    pl.o_acc_pnl = c.take((size_t)R * (size_t)pl.pitch * 8);
+    pl.o_acc_cnt = c.take((size_t)R * (size_t)pl.pitch * 8);
+    pl.acc_bytes = c.end - pl.o_acc_pnl;
+    pl.o_pnl = c.take((size_t)T * 8);
+    pl.o_equity = c.take((size_t)T * 8);
+    pl.o_long = c.take((size_t)T * 4);
+    pl.o_short = c.take((size_t)T * 4);
+    pl.o_sum = c.take(sizeof(bt_pf_summary));
+    pl.out_bytes = pl.o_sum + sizeof(bt_pf_summary) - pl.o_pnl;
+    pl.staging_bytes = c.staging_bytes();
+    return pl;
+}
+
 // ---------------------------------------------------------------------- top-k of given records
 TopkOfPlan plan_topk_of(int32_t S, int32_t P) {
     TopkOfPlan pl{};

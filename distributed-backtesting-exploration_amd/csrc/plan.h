@@ -133,6 +133,32 @@ struct WalkfwdPlan {
 // `budget_req`: bt_set_walkfwd_budget (0 = kWalkfwdBudget).
 WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int cus, int64_t budget_req = 0);
 
+// What a portfolio (k_portfolio.hip, bt_portfolio) of n entries over T bars is launched with. The
+// walk's workgroups (one wave per entry) add into R replicas of two per-bar accumulators of
+// `pitch` 8-byte words each (entry b uses replica b % R), so that the waves, which all start at
+// tile 0 together, do not meet on one row. R is the largest power of two that is at most
+// kPortfolioMaxReplicas, at most n, and whose accumulators fit kPortfolioAccBudget; at least 1
+// (T = 2^22: 64 MB). The staging is O(R * T + n), never n * T: the entry descriptors, the two
+// accumulators, then the four output rows and the summary next to each other (one copy brings
+// them back).
+constexpr int32_t kPortfolioMaxReplicas = 64;
+constexpr size_t kPortfolioAccBudget = 64u << 20;
+struct PortfolioPlan {
+    int32_t R;                     // accumulator replicas
+    int32_t finish_block;          // threads of the finish block (a multiple of 64, at most 1024)
+    int64_t pitch;                 // words per accumulator row: T rounded up to a 64-bar tile
+    int32_t tiles;                 // 64-bar tiles of the T bars
+    double fill;                   // walk waves in units of what the device holds at once (8 per SIMD)
+    size_t o_lanes, o_acc_pnl, o_acc_cnt, o_pnl, o_equity, o_long, o_short, o_sum;
+    size_t acc_bytes;              // the two accumulators, o_acc_pnl onward: zeroed before the walk
+    size_t out_bytes;              // o_pnl to the end of the summary
+    size_t staging_bytes;
+};
+// `replicas_req`: bt_set_portfolio_replicas (0 = the rule above; else that many, at most
+// kPortfolioMaxReplicas and halved until the accumulators fit the budget); `budget_req`: 0 =
+// kPortfolioAccBudget (tests only: the ABI has no setter).
+PortfolioPlan plan_portfolio(int32_t n, int32_t T, int cus, int32_t replicas_req = 0, size_t budget_req = 0);
+
 // The staging of a top-k chain over a caller's S x P records (k_topk.hip, bt_topk_of): what the
 // call uploads (order keys, summaries, one SymDesc per row) and a TopkWork of its own, so that the
 // engine's own top-k buffers are never touched: the 4,096-bin histogram, the selection state,

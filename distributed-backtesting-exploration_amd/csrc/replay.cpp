@@ -2,7 +2,6 @@
 #include "replay.h"
 
 #include <algorithm>
-#include <unordered_map>
 
 namespace bt {
 
@@ -19,12 +18,16 @@ std::string replay_refusal(bool have_dataset, int64_t n, int64_t trade_cap, bool
     return "";
 }
 
-std::string replay_resolve(const SymDesc* syms, size_t n_sym, int32_t P, int32_t n, const bt_lane* lanes,
-                           bool curves, int64_t stride, std::vector<ReplayLane>& req, int32_t& W) {
-    // global symbol id -> row; the first row of a repeated id wins
+std::unordered_map<int32_t, int32_t> symbol_rows(const SymDesc* syms, size_t n_sym) {
     std::unordered_map<int32_t, int32_t> row;
     row.reserve(n_sym);
     for (size_t s = 0; s < n_sym; ++s) row.emplace(syms[s].id, (int32_t)s);
+    return row;
+}
+
+std::string replay_resolve(const SymDesc* syms, size_t n_sym, int32_t P, int32_t n, const bt_lane* lanes,
+                           bool curves, int64_t stride, std::vector<ReplayLane>& req, int32_t& W) {
+    const std::unordered_map<int32_t, int32_t> row = symbol_rows(syms, n_sym);
     req.resize((size_t)std::max(n, 0));
     W = 0;
     for (int32_t i = 0; i < n; ++i) {

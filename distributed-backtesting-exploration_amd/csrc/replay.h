@@ -2,6 +2,7 @@
 // resolution of the requested lanes against the dataset, shared by replay.cpp and analysis.cpp.
 // No HIP call: replay.cpp builds host-only (tests/plan/replay_plan_driver.cpp).
 #pragma once
+#include <unordered_map>
 #include <vector>
 
 #include "internal.h"
@@ -12,6 +13,9 @@ namespace bt {
 // the dataset, n, trade_cap against the trades buffer and, for n > 0, the lanes and summaries.
 std::string replay_refusal(bool have_dataset, int64_t n, int64_t trade_cap, bool have_trades,
                            bool have_lanes, bool have_sum);
+
+// Global symbol id -> dataset row; the first row of a repeated id wins (bt_replay, bt_portfolio).
+std::unordered_map<int32_t, int32_t> symbol_rows(const SymDesc* syms, size_t n_sym);
 
 // The n requests against the dataset's rows: global symbol id -> the first row with that id, the
 // param against [0, P), and with curves the stride against W, the longest requested symbol.

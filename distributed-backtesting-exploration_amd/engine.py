@@ -69,6 +69,17 @@ WF_STEP_DTYPE = np.dtype([
 ])
 assert FOLD_DTYPE.itemsize == 80 and WF_STEP_DTYPE.itemsize == 104
 WALKFWD_FOLDS_MAX = 1 << 22  # fold records Engine.walk_forward(folds=True) returns
+# include/bt.h bt_pf_lane and bt_pf_summary: one entry of a portfolio and the summary of its bars
+# (docs/portfolio_spec.md)
+PF_LANE_DTYPE = np.dtype([("sym", "<i4"), ("param", "<i4"), ("from_bar", "<i4"), ("to_bar", "<i4")])
+PF_SUMMARY_DTYPE = np.dtype([
+    ("n_lanes", "<i4"), ("first_bar", "<i4"), ("n_bars", "<i4"), ("max_gross", "<i4"),
+    ("pnl", "<i8"), ("mdd", "<i8"), ("exposure", "<i8"), ("sharpe", "<f8"),
+    ("s1_lo", "<u8"), ("s1_hi", "<i8"), ("s2_lo", "<u8"), ("s2_hi", "<i8"),
+])
+assert PF_LANE_DTYPE.itemsize == 16 and PF_SUMMARY_DTYPE.itemsize == 80
+PORTFOLIO_MAX = 1 << 20  # include/bt.h BT_PORTFOLIO_MAX: entries per Engine.portfolio call
+PF_WHOLE = 2**31 - 1  # to_bar of an entry without a window: every bar of its symbol
 
 
 class BtError(RuntimeError):
@@ -221,6 +232,13 @@ _LATE_SYMBOLS = {
     "bt_set_walkfwd_budget": (3, [C.c_void_p, C.c_int64], C.c_int32),
     "bt_walk_forward_host": (3, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_portfolio": (3, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_set_portfolio_replicas": (3, [C.c_void_p, C.c_int32], C.c_int32),
+    "bt_portfolio_host": (3, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_portfolio_merge": (3, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
 }
 _late = {}
 
@@ -498,6 +516,113 @@ def walk_forward_host(folds, sym_ids, train: int = 1, annualization: int = 252) 
     return WalkForward(None, train, steps, total[:S], f)
 
 
+@dataclass
+class Portfolio:
+    """Engine.portfolio's result (bt_portfolio, docs/portfolio_spec.md): chosen lanes traded
+    together, bar by bar."""
+    pnl: np.ndarray               # int64[T]: the book's mark-to-market change over bar t, ticks
+    equity: np.ndarray            # int64[T]: its running sum
+    n_long: np.ndarray            # int32[T]: entries in window and long after bar t
+    n_short: np.ndarray           # int32[T]
+    summary: np.ndarray           # PF_SUMMARY_DTYPE, one record (shape ())
+    annualization: int = 252      # of the Sharpe (merge_portfolios recomputes it)
+
+    def gross(self) -> np.ndarray:
+        """Positions held per bar: n_long + n_short."""
+        return self.n_long + self.n_short
+
+    def net(self) -> np.ndarray:
+        """n_long - n_short."""
+        return self.n_long - self.n_short
+
+
+def as_pf_lanes(lanes, windows=None) -> np.ndarray:
+    """The entry array of Engine.portfolio (PF_LANE_DTYPE[n]): `lanes` as PF_LANE_DTYPE records, or
+    anything as_lanes accepts with `windows`, one (from_bar, to_bar) pair for every entry or an
+    (n, 2) integer array; without windows every entry runs [0, 2^31 - 1)."""
+    if isinstance(lanes, np.ndarray) and lanes.dtype == PF_LANE_DTYPE:
+        if windows is not None:
+            raise ValueError("windows: the PF_LANE_DTYPE entries carry their own")
+        return np.ascontiguousarray(lanes.reshape(-1))
+    req = as_lanes(lanes)
+    out = np.zeros(len(req), PF_LANE_DTYPE)
+    out["sym"], out["param"] = req["sym"], req["param"]
+    out["to_bar"] = PF_WHOLE
+    if windows is not None:
+        w = np.asarray(windows)
+        if not np.issubdtype(w.dtype, np.integer) or w.shape not in ((2,), (len(req), 2)):
+            raise ValueError("windows: one (from_bar, to_bar) pair or an (n, 2) integer array")
+        if w.size and (w.min() < -2**31 or w.max() >= 2**31):
+            raise ValueError("windows: from_bar and to_bar are int32")
+        w = np.broadcast_to(w, (len(req), 2))
+        out["from_bar"], out["to_bar"] = w[:, 0], w[:, 1]
+    return out
+
+
+def walk_forward_lanes(wf: WalkForward) -> np.ndarray:
+    """The portfolio entries of a walk-forward result: every step that chose a parameter, as
+    (sym, param, oos.first_bar, oos.first_bar + oos.n_bars). Engine.portfolio of them is the
+    out-of-sample book of the changing picks stitched together."""
+    st = wf.steps.reshape(-1)
+    st = st[st["param"] >= 0]
+    out = np.zeros(len(st), PF_LANE_DTYPE)
+    out["sym"], out["param"] = st["sym"], st["param"]
+    out["from_bar"] = st["oos"]["first_bar"]
+    out["to_bar"] = st["oos"]["first_bar"] + st["oos"]["n_bars"]
+    return out
+
+
+def _pf_bufs(T):
+    T = max(int(T), 1)
+    return (np.zeros(T, np.int64), np.zeros(T, np.int64), np.zeros(T, np.int32), np.zeros(T, np.int32),
+            np.zeros(1, PF_SUMMARY_DTYPE))
+
+
+def _pf_result(bufs, T, annualization) -> Portfolio:
+    T = max(int(T), 0)
+    pnl, eq, nl, ns, summ = bufs
+    return Portfolio(pnl[:T], eq[:T], nl[:T], ns[:T], summ[0], int(annualization))
+
+
+def portfolio_host(equity, pos, n_bars, windows=None, T=None, annualization: int = 252) -> Portfolio:
+    """bt_portfolio_host: the portfolio of n entries from their curves (Replay.equity, Replay.pos
+    and Replay.n_bars of Engine.replay(curves=True)) on the CPU (no GPU needed), the scalar
+    restatement of Engine.portfolio. `windows` as in as_pf_lanes; T defaults to the longest entry."""
+    eq = np.ascontiguousarray(equity, np.int64)
+    ps = np.ascontiguousarray(pos, np.int8)
+    nb = np.ascontiguousarray(np.asarray(n_bars, np.int32))
+    if eq.ndim != 2 or ps.shape != eq.shape or nb.shape != (eq.shape[0],):
+        raise ValueError("equity and pos: n x stride arrays, n_bars: n bar counts")
+    n, stride = eq.shape
+    req = as_pf_lanes(np.zeros((n, 2), np.int32), windows)
+    if T is None:
+        T = int(nb.max()) if n else 1
+    bufs = _pf_bufs(T)
+    _check(sym("bt_portfolio_host")(n, eq.ctypes.data if eq.size else None, ps.ctypes.data if ps.size else None,
+                                    nb.ctypes.data if n else None, stride, req.ctypes.data if n else None, T,
+                                    annualization, *(b.ctypes.data for b in bufs)))
+    return _pf_result(bufs, T, annualization)
+
+
+def merge_portfolios(parts) -> Portfolio:
+    """bt_portfolio_merge: portfolios of disjoint entry sets over the same bars (shards, ranks) as
+    one: the rows add, and equity and the summary are recomputed from the sums."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_portfolios: no parts")
+    T, ann = len(parts[0].pnl), parts[0].annualization
+    if any(len(p.pnl) != T or p.annualization != ann for p in parts):
+        raise ValueError("merge_portfolios: the parts differ in their bars or annualization")
+    pnl = np.ascontiguousarray(np.stack([p.pnl for p in parts]), np.int64)
+    nl = np.ascontiguousarray(np.stack([p.n_long for p in parts]), np.int32)
+    ns = np.ascontiguousarray(np.stack([p.n_short for p in parts]), np.int32)
+    summ = np.ascontiguousarray(np.stack([p.summary for p in parts]), PF_SUMMARY_DTYPE)
+    bufs = _pf_bufs(T)
+    _check(sym("bt_portfolio_merge")(len(parts), T, pnl.ctypes.data, nl.ctypes.data, ns.ctypes.data, summ.ctypes.data,
+                                     ann, *(b.ctypes.data for b in bufs)))
+    return _pf_result(bufs, T, ann)
+
+
 class Engine:
     """One engine per GPU (one process per GPU)."""
 
@@ -727,6 +852,44 @@ class Engine:
         """Device staging budget of walk_forward in bytes: 0 = the default (256 MB). Results are
         identical whatever the budget."""
         _check(sym("bt_set_walkfwd_budget")(self._h, nbytes))
+
+    # ---- portfolio of chosen lanes (bt_portfolio, k_portfolio.hip)
+    def portfolio(self, lanes, windows=None, n_bars=None) -> Portfolio:
+        """Trade chosen (symbol id, param) lanes of the resident dataset together (bt_portfolio):
+        per bar the book's pnl, equity and long / short counts, and one summary. `lanes`: what
+        as_lanes accepts (top-k records, surface().best, pairs) with optional `windows` (one
+        (from_bar, to_bar) pair or one per entry), or PF_LANE_DTYPE records such as
+        walk_forward_lanes(wf); at most PORTFOLIO_MAX. Every entry is walked over its whole series
+        and counts on its window only. `n_bars`: the bars of the result, by default those of the
+        longest resident symbol (of the longest requested one after run_batch). run() need not have
+        been called."""
+        req = as_pf_lanes(lanes, windows)
+        T = self._longest(req["sym"]) if n_bars is None else int(n_bars)
+        bufs = _pf_bufs(T)
+        _check(sym("bt_portfolio")(self._h, len(req), req.ctypes.data if len(req) else None, T,
+                                   *(b.ctypes.data for b in bufs)))
+        return _pf_result(bufs, T, self.grid.annualization)
+
+    def _longest(self, syms) -> int:
+        """Bars of the longest resident symbol when the dataset was loaded through this object,
+        else (run_batch) of the longest of `syms`, asked from bt_replay REPLAY_MAX ids at a time."""
+        bars = self._sym_bars
+        if isinstance(bars, tuple):
+            return bars[2]
+        if isinstance(bars, dict) and bars:
+            return max(bars.values())
+        ids = np.unique(np.asarray(syms, np.int32))
+        longest = 1
+        for i in range(0, len(ids), REPLAY_MAX):
+            part = np.zeros(len(ids[i:i + REPLAY_MAX]), LANE_DTYPE)
+            part["sym"] = ids[i:i + REPLAY_MAX]
+            longest = max(longest, self._replay_stride(sym("bt_replay"), part))
+        return longest
+
+    def set_portfolio_replicas(self, r: int) -> None:
+        """Replicas of the per-bar accumulators portfolio() adds into: 0 = the planner's choice.
+        Results are identical either way."""
+        _check(sym("bt_set_portfolio_replicas")(self._h, r))
 
     def stats(self) -> dict:
         st = _Stats()

@@ -326,6 +326,64 @@ int32_t bt_set_walkfwd_budget(bt_engine* e, int64_t bytes);
 int32_t bt_walk_forward_host(int32_t S, int32_t P, int32_t K, int32_t train, const bt_fold* folds,
                              const int32_t* sym_ids, int64_t annualization, bt_wf_step* steps,
                              bt_fold* total);
+/* ---- portfolio of chosen lanes (k_portfolio.hip, portfolio.cpp; semantics: docs/portfolio_spec.md)
+ * What the book does when n chosen lanes are traded together. Entry i is lane (sym, param) of the
+ * resident dataset, walked once over its whole series, and counts on the bars [from_bar,
+ * min(to_bar, its bars, T)); repeated entries count repeatedly, an empty window contributes nothing.
+ *   pnl[t]      sum over the entries in window of E_t - E_(t-1) (E of spec §4, E_(-1) = 0), ticks;
+ *   equity[t]   pnl[0] + .. + pnl[t];
+ *   n_long[t], n_short[t]   entries in window with pos_t = +1 / -1;
+ *   summary     one bt_pf_summary of the T bars.
+ * Any output may be NULL, not all. Every figure is an integer sum or extremum: the bits do not
+ * depend on the order of the entries, on the replica count or on how the entries are split over
+ * shards (bt_portfolio_merge adds the parts). Synchronous like bt_replay: waits for the engine's
+ * streams, runs on the engine stream, copies back; bt_run need not have been called and nothing
+ * another entry point reads changes. Device staging is O(replicas * T + n), never n * T. Added
+ * within ABI 3 (additive). Returns 0, or -1 with bt_last_error naming the offending index and value
+ * (the engine stays usable): a null engine, no dataset, n < 0 or n > BT_PORTFOLIO_MAX, NULL lanes
+ * with n > 0, T < 1 or T > 2^22, all outputs NULL, an unknown symbol id, param outside [0, P),
+ * from_bar < 0, to_bar < from_bar, more than 2^30 window bars in all. n == 0 is legal: zero rows
+ * and the zero summary. */
+typedef struct bt_pf_lane {
+    int32_t sym;                      /* global symbol id (bt_topk_rec.sym, bt_wf_step.sym) */
+    int32_t param;
+    int32_t from_bar, to_bar;         /* the entry counts on bars [from_bar, to_bar) */
+} bt_pf_lane;
+typedef struct bt_pf_summary {        /* 80 bytes */
+    int32_t n_lanes;                  /* entries with a non-empty window */
+    int32_t first_bar, n_bars;        /* lo and hi - lo: the bars some window covers (0, 0 without one) */
+    int32_t max_gross;                /* max over t of n_long + n_short */
+    int64_t pnl;                      /* equity[T - 1] */
+    int64_t mdd;                      /* max over t of peak_t - equity[t], peak_t = max(0, equity[0..t]) */
+    int64_t exposure;                 /* sum over t of n_long + n_short */
+    double  sharpe;                   /* of the tick increments pnl[t] over [lo, hi) */
+    uint64_t s1_lo; int64_t s1_hi; uint64_t s2_lo; int64_t s2_hi;  /* sum pnl[t], sum pnl[t]^2 */
+} bt_pf_summary;
+#define BT_PORTFOLIO_MAX (1 << 20)    /* entries per call */
+int32_t bt_portfolio(bt_engine* e, int32_t n, const bt_pf_lane* lanes, int32_t T,
+                     int64_t* pnl,      /* [T] or NULL */
+                     int64_t* equity,   /* [T] or NULL */
+                     int32_t* n_long,   /* [T] or NULL */
+                     int32_t* n_short,  /* [T] or NULL */
+                     bt_pf_summary* summary);
+/* Replicas of the per-bar accumulators the walk adds into: 0 = the planner's choice, r = r (at
+ * most 64, and as many as fit the accumulator budget). Results are identical either way. */
+int32_t bt_set_portfolio_replicas(bt_engine* e, int32_t r);
+/* Host, no GPU needed: the scalar restatement from per-entry curves as bt_replay returns them
+ * (equity and pos rows of `stride` values, n_bars[i] bars each); lanes[i] gives entry i's window
+ * (sym and param are not read). annualization is bt_config.annualization. */
+int32_t bt_portfolio_host(int32_t n, const int64_t* equity, const int8_t* pos, const int32_t* n_bars,
+                          int64_t stride, const bt_pf_lane* lanes, int32_t T, int64_t annualization,
+                          int64_t* out_pnl, int64_t* out_equity, int32_t* out_long, int32_t* out_short,
+                          bt_pf_summary* summary);
+/* Host: `world` portfolios of disjoint entry sets over the same T bars as one. pnl, n_long and
+ * n_short are [world][T] rows, summaries [world]; the rows add, first_bar / n_bars / n_lanes merge
+ * by min / max / sum, and equity and the rest of the summary are recomputed from the merged rows
+ * by the code bt_portfolio_host finishes with. Any output may be NULL, not all. */
+int32_t bt_portfolio_merge(int32_t world, int32_t T, const int64_t* pnl, const int32_t* n_long,
+                           const int32_t* n_short, const bt_pf_summary* summaries, int64_t annualization,
+                           int64_t* out_pnl, int64_t* out_equity, int32_t* out_long, int32_t* out_short,
+                           bt_pf_summary* summary);
 /* Average device time of the dominant kernel (BT_FLAG_TIMING), and how many launches. */
 int32_t bt_kernel_timing(bt_engine* e, double* total_ms, int64_t* launches, const char** name);
 int32_t bt_reset_timing(bt_engine* e);
