@@ -13,7 +13,8 @@ from .engine import (ABI_VERSION, FOLD_DTYPE, PIPE_SLOTS, WALKFWD_FOLDS_MAX, WF_
                      TOPK_DTYPE, TOPK_OF_MAX, TRADE_DTYPE, BtError, Engine, Grid, Replay, Surface, as_lanes, build,
                      config2_grid, config3_grid, config4_grid, config5_grid, lib, merge_surfaces,
                      merge_topk, surface_host, PF_LANE_DTYPE, PF_SUMMARY_DTYPE, PORTFOLIO_MAX, Portfolio, as_pf_lanes,
-                     merge_portfolios, portfolio_host, walk_forward_lanes)
+                     merge_portfolios, portfolio_host, walk_forward_lanes, COV_MAX, WIDE_DTYPE, Covariance,
+                     covariance_host)
 
 __all__ = [
     "ABI_VERSION", "FOLD_DTYPE", "PIPE_SLOTS", "WALKFWD_FOLDS_MAX", "WF_STEP_DTYPE", "WalkForward", "walk_forward_host", "BT_BOLL", "BT_DAILY", "BT_EMA_OLS", "BT_FLAG_PARITY", "BT_FLAG_TIMING", "BT_MINUTE",
@@ -21,5 +22,6 @@ __all__ = [
     "TOPK_DTYPE", "TOPK_OF_MAX", "TRADE_DTYPE", "BtError", "Engine", "Grid", "Replay", "Surface", "as_lanes", "build",
     "config2_grid", "config3_grid", "config4_grid", "config5_grid", "lib", "merge_surfaces",
     "merge_topk", "surface_host", "PF_LANE_DTYPE", "PF_SUMMARY_DTYPE", "PORTFOLIO_MAX", "Portfolio", "as_pf_lanes",
-    "merge_portfolios", "portfolio_host", "walk_forward_lanes",
+    "merge_portfolios", "portfolio_host", "walk_forward_lanes", "COV_MAX", "WIDE_DTYPE", "Covariance",
+    "covariance_host",
 ]

@@ -1,13 +1,15 @@
 // analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of, bt_topk_of,
-// bt_walk_forward and bt_portfolio with their settings. Each call checks its arguments with the pure rules
-// of replay.h / surface.h / topk_rules.h / walkfwd.h / portfolio.h, asks plan.h for its chunks and its staging
-// layout, realises that layout in the engine's one arena (engine_state.h), launches, and copies the
-// results back before it returns. Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
+// bt_walk_forward, bt_portfolio and bt_covariance / bt_gram_of with their settings. Each call checks
+// its arguments with the pure rules of replay.h / surface.h / topk_rules.h / walkfwd.h / portfolio.h /
+// covariance.h, asks plan.h for its chunks and its staging layout, realises that layout in the
+// engine's one arena (engine_state.h), launches, and copies the results back before it returns.
+// Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "covariance.h"
 #include "engine_state.h"
 #include "portfolio.h"
 #include "replay.h"
@@ -293,9 +295,108 @@ int32_t portfolio_impl(bt_engine* e, int32_t n, const bt_pf_lane* lanes, int32_t
     return 0;
 }
 
+// ---- bt_covariance / bt_gram_of: the exact Gram matrix of per-bar increments (k_gram.hip)
+// D is zeroed, filled (by the walk, or by the caller's rows), multiplied and folded; one copy
+// brings gram and sums back.
+GramWork gram_work(uint8_t* base, const GramPlan& pl, int32_t n, int32_t T) {
+    GramWork w{};
+    w.D = at<int32_t>(base, pl.o_d);
+    w.pitch = pl.pitch;
+    w.partial = at<bt_wide>(base, pl.o_partial);
+    w.gram = at<bt_wide>(base, pl.o_gram);
+    w.sums = at<int64_t>(base, pl.o_sums);
+    w.n = n, w.T = T;
+    w.nt = pl.nt, w.tiles = pl.tiles;
+    w.chunks = pl.chunks, w.chunk_bars = pl.chunk_bars;
+    return w;
+}
+
+void gram_fetch(bt_engine* e, uint8_t* base, const GramPlan& pl, int32_t n, bt_wide* gram, int64_t* sums) {
+    e->h_gram.ensure(pl.out_bytes);
+    HIPCHK(hipMemcpyAsync(e->h_gram.p, base + pl.o_gram, pl.out_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (gram) memcpy(gram, e->h_gram.p, (size_t)n * (size_t)n * sizeof(bt_wide));
+    if (sums) memcpy(sums, e->h_gram.p + (pl.o_sums - pl.o_gram), (size_t)n * sizeof(int64_t));
+}
+
+int32_t covariance_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar,
+                        bt_wide* gram, int64_t* sums, int32_t* T_out) {
+    const char* fn = "bt_covariance";
+    if (!e) refuse(fn, "null engine");
+    std::string why = covariance_refusal(!e->syms.empty(), n, lanes != nullptr, from_bar, to_bar, gram || sums || T_out);
+    if (!why.empty()) refuse(fn, why);
+    std::vector<ReplayLane> req;
+    int32_t W = 0, T = 0;  // W: the longest requested symbol
+    why = replay_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, false, 0, req, W);
+    if (!why.empty()) refuse(fn, why);
+    why = covariance_window(from_bar, to_bar, W, T);
+    if (!why.empty()) refuse(fn, why);
+    const GramPlan pl = plan_gram(n, T, e->cus, e->gram_split);
+    why = gram_staging_refusal(pl.staging_bytes, kGramStagingMax, n, T);
+    if (!why.empty()) refuse(fn, why);
+    if (T_out) *T_out = T;
+    if (n == 0 || T == 0) {
+        if (gram) memset(gram, 0, (size_t)n * (size_t)n * sizeof(bt_wide));
+        if (sums) memset(sums, 0, (size_t)n * sizeof(int64_t));
+        return 0;
+    }
+    uint8_t* base = enter(e, pl.staging_bytes);
+    ReplayLane* d_lanes = at<ReplayLane>(base, pl.o_lanes);
+    const GramWork w = gram_work(base, pl, n, T);
+    HIPCHK(hipMemcpyAsync(d_lanes, req.data(), (size_t)n * sizeof(ReplayLane), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(base + pl.o_d, 0, pl.d_bytes, e->stream));
+    HIPCHK(launch_gram_walk(d_lanes, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, w, from_bar, from_bar + T, e->stream));
+    HIPCHK(launch_gram(w, pl, false, e->stream));
+    gram_fetch(e, base, pl, n, gram, sums);
+    return 0;
+}
+
+int32_t gram_of_impl(bt_engine* e, int32_t n, int32_t T, const int32_t* d, bt_wide* gram, int64_t* sums) {
+    const char* fn = "bt_gram_of";
+    if (!e) refuse(fn, "null engine");
+    std::string why = gram_of_refusal(n, T, d != nullptr, gram || sums);
+    if (!why.empty()) refuse(fn, why);
+    const GramPlan pl = plan_gram(n, T, e->cus, e->gram_split);
+    why = gram_staging_refusal(pl.staging_bytes, kGramStagingMax, n, T);
+    if (!why.empty()) refuse(fn, why);
+    if (n == 0 || T == 0) {
+        if (gram) memset(gram, 0, (size_t)n * (size_t)n * sizeof(bt_wide));
+        if (sums) memset(sums, 0, (size_t)n * sizeof(int64_t));
+        return 0;
+    }
+    why = gram_domain_refusal(n, T, d);
+    if (!why.empty()) refuse(fn, why);
+    uint8_t* base = enter(e, pl.staging_bytes);
+    const GramWork w = gram_work(base, pl, n, T);
+    HIPCHK(hipMemsetAsync(base + pl.o_d, 0, pl.d_bytes, e->stream));
+    HIPCHK(hipMemcpy2DAsync(w.D, (size_t)pl.pitch * sizeof(int32_t), d, (size_t)T * sizeof(int32_t),
+                            (size_t)T * sizeof(int32_t), (size_t)n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_gram(w, pl, true, e->stream));
+    gram_fetch(e, base, pl, n, gram, sums);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t bt_covariance(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar, bt_wide* gram,
+                      int64_t* sums, int32_t* T_out) {
+    ABI_GUARD(-1, { return covariance_impl(e, n, lanes, from_bar, to_bar, gram, sums, T_out); })
+}
+
+int32_t bt_gram_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, bt_wide* gram, int64_t* sums) {
+    ABI_GUARD(-1, { return gram_of_impl(e, n, T, d, gram, sums); })
+}
+
+int32_t bt_set_gram_split(bt_engine* e, int32_t k) {
+    ABI_GUARD(-1, {
+        if (!e) refuse("bt_set_gram_split", "null engine");
+        if (k < 0) refuse("bt_set_gram_split", "k = " + std::to_string(k) + " is negative");
+        e->gram_split = k;
+        return 0;
+    })
+}
 
 int32_t bt_portfolio(bt_engine* e, int32_t n, const bt_pf_lane* lanes, int32_t T, int64_t* pnl, int64_t* equity,
                      int32_t* n_long, int32_t* n_short, bt_pf_summary* summary) {

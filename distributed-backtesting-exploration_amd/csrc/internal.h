@@ -212,6 +212,30 @@ hipError_t launch_portfolio(const PfLane* lanes, int32_t n, const int32_t* high,
                             const int32_t* close, const Grid& g, const PfWork& w, const PortfolioPlan& pl,
                             hipStream_t st);
 
+// Covariance of chosen lanes (k_gram.hip, bt_covariance / bt_gram_of; docs/covariance_spec.md).
+// The walk (one wave64 workgroup per lane) writes the lane's increments over the window into row i
+// of the int32 matrix D and its row sum; the product (one wave per 16 x 16 tile with I <= J and
+// bar chunk) forms D * D^T on the fp64 matrix cores and leaves one exact int128 per element and
+// chunk; the fold adds the chunks, mirrors the upper triangle and writes gram[n][n] (and the row
+// sums of a staged D). The host zeroes D before the walk or the upload: its padding is zero.
+struct GramWork {
+    int32_t* D;                    // [n][pitch] increments, column t - from_bar
+    int64_t pitch;                 // elements per row: T rounded up to 64
+    bt_wide* partial;              // [chunks][tiles][256], tile (I, J) of I <= J at I*nt - I*(I-1)/2 + J - I
+    bt_wide* gram;                 // [n][n]
+    int64_t* sums;                 // [n]
+    int32_t n, T;
+    int32_t nt;                    // 16-row tiles along n
+    int32_t tiles;                 // nt * (nt + 1) / 2
+    int32_t chunks, chunk_bars;    // bar chunks and the bars of one (a multiple of 64)
+};
+struct GramPlan;
+hipError_t launch_gram_walk(const ReplayLane* lanes, const int32_t* high, const int32_t* low,
+                            const int32_t* close, const Grid& g, const GramWork& w, int32_t from, int32_t to,
+                            hipStream_t st);
+// `staged`: D was uploaded (bt_gram_of) and the fold writes the row sums too.
+hipError_t launch_gram(const GramWork& w, const GramPlan& pl, bool staged, hipStream_t st);
+
 // Reductions of an S x P summary matrix (k_surface.hip, bt_surface / bt_surface_of): one pass over
 // the records writes per-chunk column aggregates and per-tile row winners, two short kernels fold
 // them into agg[P] and best[S]. Symbol s has id ids[s * id_stride] (the engine's SymDesc array or

@@ -494,6 +494,44 @@ PortfolioPlan plan_portfolio(int32_t n, int32_t T, int cus, int32_t replicas_req
     return pl;
 }
 
+// ------------------------------------------------------------------------ covariance of lanes
+GramPlan plan_gram(int32_t n, int32_t T, int cus, int32_t split_req) {
+    GramPlan pl{};
+    n = std::max(n, 0);
+    T = std::max(T, 0);
+    pl.nt = (n + 15) / 16;
+    pl.tiles = pl.nt * (pl.nt + 1) / 2;
+    const int64_t groups = std::max<int64_t>(1, ((int64_t)T + kTile - 1) / kTile);  // 64-bar groups
+    pl.pitch = groups * kTile;
+    const size_t chunk_partial = (size_t)pl.tiles * 256 * sizeof(bt_wide);
+    // as many chunks as the partial budget holds, and never more than one per group
+    int64_t most = chunk_partial ? std::max<size_t>(1, kGramPartialBudget / chunk_partial) : 1;
+    most = std::min<int64_t>(std::min<int64_t>(most, groups), 65535);
+    int64_t chunks = 1;
+    if (split_req > 0) {
+        chunks = split_req;
+    } else if (pl.tiles > 0) {
+        const int64_t want = (int64_t)std::max(cus, 1) * kGramWavesPerCu;
+        chunks = std::min<int64_t>((want + pl.tiles - 1) / pl.tiles, pl.pitch / kGramMinChunkBars);
+    }
+    chunks = std::max<int64_t>(1, std::min(chunks, most));
+    const int64_t per = (groups + chunks - 1) / chunks;  // groups per chunk: none is empty
+    pl.chunk_bars = (int32_t)(per * kTile);
+    pl.chunks = (int32_t)((groups + per - 1) / per);
+    pl.fold_block = 256;
+    pl.fill = (double)pl.tiles * pl.chunks / ((double)std::max(cus, 1) * kGramWavesPerCu);
+    Carve c;
+    pl.o_lanes = c.take((size_t)n * sizeof(ReplayLane));
+    pl.o_d = c.take((size_t)n * (size_t)pl.pitch * sizeof(int32_t));
+    pl.d_bytes = c.end - pl.o_d;
+    pl.o_partial = c.take((size_t)pl.chunks * chunk_partial);
+    pl.o_gram = c.take((size_t)n * (size_t)n * sizeof(bt_wide));
+    pl.o_sums = c.take((size_t)n * sizeof(int64_t));
+    pl.out_bytes = pl.o_sums + (size_t)n * sizeof(int64_t) - pl.o_gram;
+    pl.staging_bytes = c.staging_bytes();
+    return pl;
+}
+
 // ---------------------------------------------------------------------- top-k of given records
 TopkOfPlan plan_topk_of(int32_t S, int32_t P) {
     TopkOfPlan pl{};

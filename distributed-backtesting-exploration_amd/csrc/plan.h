@@ -159,6 +159,32 @@ struct PortfolioPlan {
 // kPortfolioAccBudget (tests only: the ABI has no setter).
 PortfolioPlan plan_portfolio(int32_t n, int32_t T, int cus, int32_t replicas_req = 0, size_t budget_req = 0);
 
+// What a Gram product (k_gram.hip, bt_covariance / bt_gram_of) of n lanes over T bars is launched
+// with. D holds one row of `pitch` int32 per lane (T rounded up to 64; the padding is zero) and the
+// product runs one wave per 16 x 16 tile of the upper triangle (rows past n read as zero) and bar
+// chunk. A small n with a long T has few tiles (64 lanes: 10), so the bars are cut into `chunks`
+// chunks of chunk_bars (a multiple of 64, the last one shorter; none empty) until the device holds
+// kGramWavesPerCu waves per CU, a chunk keeping at least kGramMinChunkBars bars and the partials
+// kGramPartialBudget bytes; a large n gets one chunk. The staging: the lane descriptors, D, the
+// chunk partials, then gram[n][n] and sums[n] next to each other (one copy brings both back).
+constexpr int kGramWavesPerCu = 8;
+constexpr int32_t kGramMinChunkBars = 512;
+constexpr size_t kGramPartialBudget = 64u << 20;
+constexpr size_t kGramStagingMax = 256u << 20;   // the call is refused above it
+struct GramPlan {
+    int32_t nt, tiles;             // 16-row tiles along n; tiles of the upper triangle
+    int32_t chunks, chunk_bars;
+    int32_t fold_block;            // threads of a fold block (a multiple of 64)
+    int64_t pitch;
+    double fill;                   // product waves in units of kGramWavesPerCu per CU
+    size_t o_lanes, o_d, o_partial, o_gram, o_sums;
+    size_t d_bytes;                // D: zeroed before the walk or the upload
+    size_t out_bytes;              // o_gram to the end of the sums
+    size_t staging_bytes;
+};
+// `split_req`: bt_set_gram_split (0 = the rule above; else that many chunks, at most one per 64 bars).
+GramPlan plan_gram(int32_t n, int32_t T, int cus, int32_t split_req = 0);
+
 // The staging of a top-k chain over a caller's S x P records (k_topk.hip, bt_topk_of): what the
 // call uploads (order keys, summaries, one SymDesc per row) and a TopkWork of its own, so that the
 // engine's own top-k buffers are never touched: the 4,096-bin histogram, the selection state,

@@ -80,6 +80,10 @@ PF_SUMMARY_DTYPE = np.dtype([
 assert PF_LANE_DTYPE.itemsize == 16 and PF_SUMMARY_DTYPE.itemsize == 80
 PORTFOLIO_MAX = 1 << 20  # include/bt.h BT_PORTFOLIO_MAX: entries per Engine.portfolio call
 PF_WHOLE = 2**31 - 1  # to_bar of an entry without a window: every bar of its symbol
+# include/bt.h bt_wide: an int128 as lo/hi words (docs/covariance_spec.md)
+WIDE_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<i8")])
+assert WIDE_DTYPE.itemsize == 16
+COV_MAX = 2048  # include/bt.h BT_COV_MAX: lanes per Engine.covariance call
 
 
 class BtError(RuntimeError):
@@ -239,6 +243,12 @@ _LATE_SYMBOLS = {
                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
     "bt_portfolio_merge": (3, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_covariance": (3, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                          C.c_void_p], C.c_int32),
+    "bt_gram_of": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_set_gram_split": (3, [C.c_void_p, C.c_int32], C.c_int32),
+    "bt_covariance_host": (3, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                               C.c_void_p, C.c_void_p], C.c_int32),
 }
 _late = {}
 
@@ -623,6 +633,95 @@ def merge_portfolios(parts) -> Portfolio:
     return _pf_result(bufs, T, ann)
 
 
+@dataclass
+class Covariance:
+    """Engine.covariance's result (bt_covariance, docs/covariance_spec.md): the exact Gram matrix
+    of the lanes' per-bar pnl increments over one window, and what follows from it. The float
+    methods work on gram_f64, each step a single IEEE double operation in the order written."""
+    wide: np.ndarray              # WIDE_DTYPE[n, n]: the Gram matrix as the library returns it
+    sums: np.ndarray              # int64[n]: the sum of each lane's increments
+    n_bars: int                   # T, the bars of the window
+
+    @property
+    def gram(self) -> np.ndarray:
+        """[n, n] Python ints."""
+        out = np.empty(self.wide.shape, object)
+        flat = out.reshape(-1)
+        for k, (lo, hi) in enumerate(zip(self.wide["lo"].reshape(-1).tolist(), self.wide["hi"].reshape(-1).tolist())):
+            flat[k] = (hi << 64) | lo
+        return out
+
+    @property
+    def gram_f64(self) -> np.ndarray:
+        """[n, n] doubles, every entry through bt_i128_to_double: one rounding."""
+        out = np.empty(self.wide.shape, np.float64)
+        flat = out.reshape(-1)
+        for k, (lo, hi) in enumerate(zip(self.wide["lo"].reshape(-1).tolist(), self.wide["hi"].reshape(-1).tolist())):
+            flat[k] = i128_to_double(lo, hi)
+        return out
+
+    def cov(self) -> np.ndarray:
+        """gram_f64 / T - outer(sums / T, sums / T); zeros when the window has no bar."""
+        n = len(self.sums)
+        if self.n_bars < 1:
+            return np.zeros((n, n))
+        T = float(self.n_bars)
+        m = self.sums.astype(np.float64) / T
+        return self.gram_f64 / T - np.outer(m, m)
+
+    def vol(self) -> np.ndarray:
+        """The root of cov's diagonal, 0 where a variance is not positive."""
+        v = np.diagonal(self.cov())
+        return np.sqrt(np.where(v > 0, v, 0.0))
+
+    def corr(self) -> np.ndarray:
+        """cov over the root of the diagonal products, 0 where a variance is not positive."""
+        c = self.cov()
+        v = np.diagonal(c)
+        ok = v > 0
+        den = np.sqrt(np.outer(np.where(ok, v, 1.0), np.where(ok, v, 1.0)))
+        return np.where(np.outer(ok, ok), c / den, 0.0)
+
+    def book_s2(self, weights=None) -> int:
+        """w^T gram w in Python ints, exact, for integer weights; all ones by default: the s2 of
+        the portfolio of the same lanes over the same window."""
+        n = len(self.sums)
+        w = [1] * n if weights is None else [int(x) for x in weights]
+        if len(w) != n or (weights is not None and any(int(x) != x for x in weights)):
+            raise ValueError("book_s2: one integer weight per lane")
+        g = self.gram
+        return sum(w[i] * w[j] * g[i, j] for i in range(n) for j in range(n))
+
+
+def _window(window):
+    if window is None:
+        return 0, PF_WHOLE
+    w = np.asarray(window)
+    if w.shape != (2,) or not np.issubdtype(w.dtype, np.integer) or w.min() < -2**31 or w.max() >= 2**31:
+        raise ValueError("window: one (from_bar, to_bar) pair of int32")
+    return int(w[0]), int(w[1])
+
+
+def _cov_result(n, wide, sums, T) -> Covariance:
+    return Covariance(wide[:n * n].reshape(n, n), sums[:n], int(T))
+
+
+def covariance_host(equity, n_bars, window=None) -> Covariance:
+    """bt_covariance_host: the covariance of n lanes from their replayed equity curves
+    (Replay.equity and Replay.n_bars of Engine.replay(curves=True)) on the CPU (no GPU needed), the
+    scalar restatement of Engine.covariance."""
+    eq = np.ascontiguousarray(equity, np.int64)
+    nb = np.ascontiguousarray(np.asarray(n_bars, np.int32))
+    if eq.ndim != 2 or nb.shape != (eq.shape[0],):
+        raise ValueError("equity: an n x stride array, n_bars: n bar counts")
+    n, stride = eq.shape
+    frm, to = _window(window)
+    wide, sums, T = np.zeros(max(n * n, 1), WIDE_DTYPE), np.zeros(max(n, 1), np.int64), C.c_int32(0)
+    _check(sym("bt_covariance_host")(n, eq.ctypes.data if eq.size else None, nb.ctypes.data if n else None, stride,
+                                     frm, to, wide.ctypes.data, sums.ctypes.data, C.addressof(T)))
+    return _cov_result(n, wide, sums, T.value)
+
+
 class Engine:
     """One engine per GPU (one process per GPU)."""
 
@@ -890,6 +989,41 @@ class Engine:
         """Replicas of the per-bar accumulators portfolio() adds into: 0 = the planner's choice.
         Results are identical either way."""
         _check(sym("bt_set_portfolio_replicas")(self._h, r))
+
+    # ---- covariance of chosen lanes (bt_covariance / bt_gram_of, k_gram.hip)
+    def covariance(self, lanes, window=None) -> Covariance:
+        """How chosen (symbol id, param) lanes of the resident dataset move together
+        (bt_covariance): the exact Gram matrix and the sums of their per-bar pnl increments over
+        one common window, by default every bar of the longest requested symbol. `lanes`: what
+        replay takes (read_topk(), surface().best, pairs), at most COV_MAX. run() need not have
+        been called."""
+        req = as_lanes(lanes)
+        n = len(req)
+        frm, to = _window(window)
+        wide, sums, T = np.zeros(max(n * n, 1), WIDE_DTYPE), np.zeros(max(n, 1), np.int64), C.c_int32(0)
+        _check(sym("bt_covariance")(self._h, n, req.ctypes.data if n else None, frm, to, wide.ctypes.data,
+                                    sums.ctypes.data, C.addressof(T)))
+        return _cov_result(n, wide, sums, T.value)
+
+    def gram_of(self, d) -> Covariance:
+        """The Gram kernels (bt_gram_of) on a caller's increments: an [n, T] integer array with
+        |d| < 2^31, n at most COV_MAX. Needs no dataset."""
+        a = np.asarray(d)
+        if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("gram_of: an n x T integer array")
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise ValueError("gram_of: the increments are int32")
+        a = np.ascontiguousarray(a, np.int32)
+        n, T = a.shape
+        wide, sums = np.zeros(max(n * n, 1), WIDE_DTYPE), np.zeros(max(n, 1), np.int64)
+        _check(sym("bt_gram_of")(self._h, n, T, a.ctypes.data if a.size else None, wide.ctypes.data,
+                                 sums.ctypes.data))
+        return _cov_result(n, wide, sums, T)
+
+    def set_gram_split(self, k: int) -> None:
+        """Bar chunks covariance() and gram_of() cut their window into: 0 = the planner's choice.
+        Results are identical either way."""
+        _check(sym("bt_set_gram_split")(self._h, k))
 
     def stats(self) -> dict:
         st = _Stats()

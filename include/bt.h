@@ -384,6 +384,47 @@ int32_t bt_portfolio_merge(int32_t world, int32_t T, const int64_t* pnl, const i
                            const int32_t* n_short, const bt_pf_summary* summaries, int64_t annualization,
                            int64_t* out_pnl, int64_t* out_equity, int32_t* out_long, int32_t* out_short,
                            bt_pf_summary* summary);
+/* ---- covariance of chosen lanes (k_gram.hip, covariance.cpp; semantics: docs/covariance_spec.md)
+ * How n chosen lanes move together over one common window [from_bar, to_bar). With B_max the bars
+ * of the longest requested symbol, to' = min(to_bar, B_max) and T = max(0, to' - from_bar), lane
+ * i, walked once over its whole series, gives the increments d_t = E_t - E_(t-1) (E of spec §4,
+ * E_(-1) = 0) on the window's bars below its own bar count and 0 on the others.
+ *   gram[i*n + j]  sum over the window of d^i_t * d^j_t: an exact int128 (bt_wide, lo/hi words
+ *                  like bt_sums), symmetric, |gram| < 2^84;
+ *   sums[i]        sum over the window of d^i_t, int64 (below 2^53);
+ *   T_out          T.
+ * Every figure is an exact integer sum: the bits do not depend on the bar chunks the device cuts the
+ * window into, and the grams of disjoint windows add to the gram of their union. The sum of all
+ * gram entries is the s2 of the bt_portfolio of the same lanes over the same window, the sum of
+ * sums its s1. Any output may be NULL, not all; with n == 0 or T == 0 every output is zero.
+ * Synchronous like bt_replay: waits for the engine's streams, runs on the engine stream, copies
+ * back; bt_run need not have been called and nothing another entry point reads changes. Added
+ * within ABI 3 (additive). Returns 0, or -1 with bt_last_error naming the offending index and value
+ * (the engine stays usable): a null engine, no dataset, n < 0 or n > BT_COV_MAX, NULL lanes with
+ * n > 0, an unknown symbol id, param outside [0, P), from_bar < 0, to_bar < from_bar, T > 2^22, all
+ * outputs NULL, a device staging need above 256 MB (n rows of T increments, the chunk partials and
+ * the n x n result; the bytes are named). */
+typedef struct bt_wide {              /* an int128: value = hi * 2^64 + lo */
+    uint64_t lo;
+    int64_t hi;
+} bt_wide;
+#define BT_COV_MAX 2048               /* lanes per call */
+int32_t bt_covariance(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar,
+                      bt_wide* gram,      /* [n * n] or NULL */
+                      int64_t* sums,      /* [n] or NULL */
+                      int32_t* T_out);    /* or NULL */
+/* The same Gram kernels on a caller's increments d[n][T] (row-major int32, |d| < 2^31: INT32_MIN
+ * is refused, with its index named): the way to the extremes of the exactness argument, which a
+ * real series cannot reach. Works on any engine (also one without a dataset). n in [0, BT_COV_MAX],
+ * T in [0, 2^22]; gram and/or sums (not both NULL). */
+int32_t bt_gram_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, bt_wide* gram, int64_t* sums);
+/* Bar chunks the Gram product is cut into (split-K): 0 = the planner's choice, k = k (at most one
+ * per 64 bars). Results are identical either way. */
+int32_t bt_set_gram_split(bt_engine* e, int32_t k);
+/* Host, no GPU needed: the scalar restatement from replayed curves (equity rows of `stride` values,
+ * n_bars[i] bars each, as bt_replay returns them). B_max is the largest n_bars[i]. */
+int32_t bt_covariance_host(int32_t n, const int64_t* equity, const int32_t* n_bars, int64_t stride,
+                           int32_t from_bar, int32_t to_bar, bt_wide* gram, int64_t* sums, int32_t* T_out);
 /* Average device time of the dominant kernel (BT_FLAG_TIMING), and how many launches. */
 int32_t bt_kernel_timing(bt_engine* e, double* total_ms, int64_t* launches, const char** name);
 int32_t bt_reset_timing(bt_engine* e);
