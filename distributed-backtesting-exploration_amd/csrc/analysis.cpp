@@ -23,7 +23,7 @@ namespace {
 
 [[noreturn]] void refuse(const char* fn, const std::string& why) { throw HipFail{std::string(fn) + ": " + why}; }
 
-// Every analysis call starts here, after its refusals: both streams drained, then the arena grown
+// Every analysis call starts here, after its refusals: every stream drained, then the arena grown
 // to the call's plan. With the wait on the engine stream before the call returns this is the
 // invariant the shared arena rests on (engine_state.h).
 uint8_t* enter(bt_engine* e, size_t staging_bytes) {
@@ -66,26 +66,26 @@ int32_t replay_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade
     // copy and the host tails zeroed here
     auto fetch = [&](void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t m) {
         if (dst_pitch == src_pitch) {
-            HIPCHK(hipMemcpyAsync(dst, src, m * src_pitch, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipMemcpyAsync(dst, src, m * src_pitch, hipMemcpyDeviceToHost, main_stream(e)));
             return;
         }
-        HIPCHK(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, src_pitch, m, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, src_pitch, m, hipMemcpyDeviceToHost, main_stream(e)));
         for (size_t i = 0; i < m; ++i)
             memset(static_cast<uint8_t*>(dst) + i * dst_pitch + src_pitch, 0, dst_pitch - src_pitch);
     };
     for_chunks((size_t)n, (size_t)pl.lanes_per_chunk, [&](size_t i0, size_t m) {
-        HIPCHK(hipMemcpyAsync(d_lanes, req.data() + i0, m * sizeof(ReplayLane), hipMemcpyHostToDevice, e->stream));
-        if (dcap) HIPCHK(hipMemsetAsync(out.trades, 0, m * dcap * sizeof(bt_trade), e->stream));
-        if (equity) HIPCHK(hipMemsetAsync(out.equity, 0, m * pitch * 8, e->stream));
-        if (pos) HIPCHK(hipMemsetAsync(out.pos, 0, m * pitch, e->stream));
-        HIPCHK(launch_replay(d_lanes, (int32_t)m, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, out, e->stream));
-        HIPCHK(hipMemcpyAsync(sum + i0, out.sum, m * sizeof(bt_summary), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(d_lanes, req.data() + i0, m * sizeof(ReplayLane), hipMemcpyHostToDevice, main_stream(e)));
+        if (dcap) HIPCHK(hipMemsetAsync(out.trades, 0, m * dcap * sizeof(bt_trade), main_stream(e)));
+        if (equity) HIPCHK(hipMemsetAsync(out.equity, 0, m * pitch * 8, main_stream(e)));
+        if (pos) HIPCHK(hipMemsetAsync(out.pos, 0, m * pitch, main_stream(e)));
+        HIPCHK(launch_replay(d_lanes, (int32_t)m, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, out, main_stream(e)));
+        HIPCHK(hipMemcpyAsync(sum + i0, out.sum, m * sizeof(bt_summary), hipMemcpyDeviceToHost, main_stream(e)));
         if (dcap)
             fetch(trades + i0 * (size_t)trade_cap, (size_t)trade_cap * sizeof(bt_trade), out.trades,
                   dcap * sizeof(bt_trade), m);
         if (equity) fetch(equity + i0 * (size_t)stride, (size_t)stride * 8, out.equity, pitch * 8, m);
         if (pos) fetch(pos + i0 * (size_t)stride, (size_t)stride, out.pos, pitch, m);
-        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipStreamSynchronize(main_stream(e)));
     });
     if (n_bars)
         for (int32_t i = 0; i < n; ++i) n_bars[i] = req[i].bars;
@@ -104,14 +104,14 @@ void surface_launch(bt_engine* e, const SurfacePlan& pl, uint8_t* base, const bt
     w.best_partial = at<bt_topk_rec>(base, pl.o_best_partial);
     w.agg = agg ? at<bt_param_agg>(base, pl.o_agg) : nullptr;
     w.best = best ? at<bt_topk_rec>(base, pl.o_best) : nullptr;
-    HIPCHK(launch_surface(d_sum, d_ids, id_stride, S, P, pl, w, e->stream));
+    HIPCHK(launch_surface(d_sum, d_ids, id_stride, S, P, pl, w, main_stream(e)));
     // the results lie next to each other: one copy into pinned memory, whatever was asked for
     const size_t n_agg = (size_t)P * sizeof(bt_param_agg), n_best = (size_t)S * sizeof(bt_topk_rec);
     const size_t lo = agg ? pl.o_agg : pl.o_best, hi = best && S > 0 ? pl.o_best + n_best : pl.o_agg + n_agg;
     if (hi <= lo) return;  // best alone of a matrix without rows
     e->h_surface.ensure(hi - lo);
-    HIPCHK(hipMemcpyAsync(e->h_surface.p, base + lo, hi - lo, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_surface.p, base + lo, hi - lo, hipMemcpyDeviceToHost, main_stream(e)));
+    HIPCHK(hipStreamSynchronize(main_stream(e)));
     if (agg) memcpy(agg, e->h_surface.p + (pl.o_agg - lo), n_agg);
     if (best && S > 0) memcpy(best, e->h_surface.p + (pl.o_best - lo), n_best);
 }
@@ -146,8 +146,8 @@ int32_t surface_of_impl(bt_engine* e, int32_t S, int32_t P, const bt_summary* su
     bt_summary* d_sum = at<bt_summary>(base, pl.o_sum);
     int32_t* d_ids = at<int32_t>(base, pl.o_ids);
     if (S > 0) {
-        HIPCHK(hipMemcpyAsync(d_sum, sum, (size_t)S * (size_t)P * sizeof(bt_summary), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipMemcpyAsync(d_ids, ids, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(d_sum, sum, (size_t)S * (size_t)P * sizeof(bt_summary), hipMemcpyHostToDevice, main_stream(e)));
+        HIPCHK(hipMemcpyAsync(d_ids, ids, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, main_stream(e)));
     }
     surface_launch(e, pl, base, d_sum, d_ids, 1, S, P, agg, best);
     return 0;
@@ -179,15 +179,15 @@ int32_t topk_of_impl(bt_engine* e, int32_t S, int32_t P, const bt_summary* sum, 
     const TopkWork w{at<unsigned int>(base, pl.o_hist),      at<unsigned long long>(base, pl.o_state),
                      at<unsigned int>(base, pl.o_counts),    at<unsigned long long>(base, pl.o_above),
                      at<unsigned long long>(base, pl.o_cand), kTopkCap, d_out + 1, reinterpret_cast<int32_t*>(d_out)};
-    HIPCHK(hipMemcpyAsync(d_key, key.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_sum, sum, n * sizeof(bt_summary), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_syms, syms.data(), (size_t)S * sizeof(SymDesc), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(d_out, 0, ((size_t)kTopkMax + 1) * sizeof(bt_topk_rec), e->stream));
-    HIPCHK(launch_topk_init(w, e->stream));
-    HIPCHK(launch_topk(d_key, d_sum, d_syms, (int64_t)n, P, k, w, e->stream, lds_free_hist != 0));
+    HIPCHK(hipMemcpyAsync(d_key, key.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, main_stream(e)));
+    HIPCHK(hipMemcpyAsync(d_sum, sum, n * sizeof(bt_summary), hipMemcpyHostToDevice, main_stream(e)));
+    HIPCHK(hipMemcpyAsync(d_syms, syms.data(), (size_t)S * sizeof(SymDesc), hipMemcpyHostToDevice, main_stream(e)));
+    HIPCHK(hipMemsetAsync(d_out, 0, ((size_t)kTopkMax + 1) * sizeof(bt_topk_rec), main_stream(e)));
+    HIPCHK(launch_topk_init(w, main_stream(e)));
+    HIPCHK(launch_topk(d_key, d_sum, d_syms, (int64_t)n, P, k, w, main_stream(e), lds_free_hist != 0));
     std::vector<bt_topk_rec> got((size_t)k + 1);
-    HIPCHK(hipMemcpyAsync(got.data(), d_out, got.size() * sizeof(bt_topk_rec), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpyAsync(got.data(), d_out, got.size() * sizeof(bt_topk_rec), hipMemcpyDeviceToHost, main_stream(e)));
+    HIPCHK(hipStreamSynchronize(main_stream(e)));
     int32_t count;
     memcpy(&count, &got[0], sizeof count);
     if (count < 0 || count > k) refuse(fn, "the device wrote a count of " + std::to_string(count));
@@ -216,7 +216,7 @@ int32_t walk_forward_impl(bt_engine* e, int32_t K, const int32_t* bounds, int32_
     const bool select = steps || total;
     const int32_t n_steps = select ? walkfwd_steps(K, train) : 0;
     const size_t row_recs = (size_t)K * (size_t)P;
-    HIPCHK(hipMemcpyAsync(base, bounds, ((size_t)K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(base, bounds, ((size_t)K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, main_stream(e)));
     WfArgs a{};
     a.bounds = at<const int32_t>(base, 0);
     a.rec = at<bt_fold>(base, pl.o_rec);
@@ -229,16 +229,16 @@ int32_t walk_forward_impl(bt_engine* e, int32_t K, const int32_t* bounds, int32_
     for_chunks((size_t)S, (size_t)pl.rows_per_chunk, [&](size_t r0, size_t m) {
         a.syms = e->d_syms.p + r0;
         a.n_rows = (int32_t)m;
-        HIPCHK(hipMemsetAsync(a.rec, 0, m * row_recs * sizeof(bt_fold), e->stream));
-        HIPCHK(launch_wf_walk(a, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, e->stream));
+        HIPCHK(hipMemsetAsync(a.rec, 0, m * row_recs * sizeof(bt_fold), main_stream(e)));
+        HIPCHK(launch_wf_walk(a, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, main_stream(e)));
         if (select) {
-            HIPCHK(launch_wf_select(a, e->grid, pl, e->stream));
+            HIPCHK(launch_wf_select(a, e->grid, pl, main_stream(e)));
             HIPCHK(hipMemcpyAsync(st + r0 * (size_t)n_steps, a.steps, m * (size_t)n_steps * sizeof(bt_wf_step),
-                                  hipMemcpyDeviceToHost, e->stream));
+                                  hipMemcpyDeviceToHost, main_stream(e)));
         }
         if (folds)
-            HIPCHK(hipMemcpyAsync(h_rec.data(), a.rec, m * row_recs * sizeof(bt_fold), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
+            HIPCHK(hipMemcpyAsync(h_rec.data(), a.rec, m * row_recs * sizeof(bt_fold), hipMemcpyDeviceToHost, main_stream(e)));
+        HIPCHK(hipStreamSynchronize(main_stream(e)));
         if (folds)   // [row][fold][param] -> the caller's [row][param][fold]
             for (size_t r = 0; r < m; ++r)
                 for (size_t k = 0; k < (size_t)K; ++k)
@@ -280,11 +280,11 @@ int32_t portfolio_impl(bt_engine* e, int32_t n, const bt_pf_lane* lanes, int32_t
     w.n_short = at<int32_t>(base, pl.o_short);
     w.sum = at<bt_pf_summary>(base, pl.o_sum);
     if (m > 0)
-        HIPCHK(hipMemcpyAsync(d_lanes, rs.req.data(), (size_t)m * sizeof(PfLane), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(base + pl.o_acc_pnl, 0, pl.acc_bytes, e->stream));
-    HIPCHK(launch_portfolio(d_lanes, m, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, w, pl, e->stream));
-    HIPCHK(hipMemcpyAsync(e->h_portfolio.p, base + pl.o_pnl, pl.out_bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipMemcpyAsync(d_lanes, rs.req.data(), (size_t)m * sizeof(PfLane), hipMemcpyHostToDevice, main_stream(e)));
+    HIPCHK(hipMemsetAsync(base + pl.o_acc_pnl, 0, pl.acc_bytes, main_stream(e)));
+    HIPCHK(launch_portfolio(d_lanes, m, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, w, pl, main_stream(e)));
+    HIPCHK(hipMemcpyAsync(e->h_portfolio.p, base + pl.o_pnl, pl.out_bytes, hipMemcpyDeviceToHost, main_stream(e)));
+    HIPCHK(hipStreamSynchronize(main_stream(e)));
     const uint8_t* h = e->h_portfolio.p;
     const size_t bars = (size_t)T;
     if (pnl) memcpy(pnl, h, bars * 8);
@@ -313,8 +313,8 @@ GramWork gram_work(uint8_t* base, const GramPlan& pl, int32_t n, int32_t T) {
 
 void gram_fetch(bt_engine* e, uint8_t* base, const GramPlan& pl, int32_t n, bt_wide* gram, int64_t* sums) {
     e->h_gram.ensure(pl.out_bytes);
-    HIPCHK(hipMemcpyAsync(e->h_gram.p, base + pl.o_gram, pl.out_bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_gram.p, base + pl.o_gram, pl.out_bytes, hipMemcpyDeviceToHost, main_stream(e)));
+    HIPCHK(hipStreamSynchronize(main_stream(e)));
     if (gram) memcpy(gram, e->h_gram.p, (size_t)n * (size_t)n * sizeof(bt_wide));
     if (sums) memcpy(sums, e->h_gram.p + (pl.o_sums - pl.o_gram), (size_t)n * sizeof(int64_t));
 }
@@ -343,10 +343,10 @@ int32_t covariance_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t f
     uint8_t* base = enter(e, pl.staging_bytes);
     ReplayLane* d_lanes = at<ReplayLane>(base, pl.o_lanes);
     const GramWork w = gram_work(base, pl, n, T);
-    HIPCHK(hipMemcpyAsync(d_lanes, req.data(), (size_t)n * sizeof(ReplayLane), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(base + pl.o_d, 0, pl.d_bytes, e->stream));
-    HIPCHK(launch_gram_walk(d_lanes, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, w, from_bar, from_bar + T, e->stream));
-    HIPCHK(launch_gram(w, pl, false, e->stream));
+    HIPCHK(hipMemcpyAsync(d_lanes, req.data(), (size_t)n * sizeof(ReplayLane), hipMemcpyHostToDevice, main_stream(e)));
+    HIPCHK(hipMemsetAsync(base + pl.o_d, 0, pl.d_bytes, main_stream(e)));
+    HIPCHK(launch_gram_walk(d_lanes, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, w, from_bar, from_bar + T, main_stream(e)));
+    HIPCHK(launch_gram(w, pl, false, main_stream(e)));
     gram_fetch(e, base, pl, n, gram, sums);
     return 0;
 }
@@ -368,10 +368,10 @@ int32_t gram_of_impl(bt_engine* e, int32_t n, int32_t T, const int32_t* d, bt_wi
     if (!why.empty()) refuse(fn, why);
     uint8_t* base = enter(e, pl.staging_bytes);
     const GramWork w = gram_work(base, pl, n, T);
-    HIPCHK(hipMemsetAsync(base + pl.o_d, 0, pl.d_bytes, e->stream));
+    HIPCHK(hipMemsetAsync(base + pl.o_d, 0, pl.d_bytes, main_stream(e)));
     HIPCHK(hipMemcpy2DAsync(w.D, (size_t)pl.pitch * sizeof(int32_t), d, (size_t)T * sizeof(int32_t),
-                            (size_t)T * sizeof(int32_t), (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(launch_gram(w, pl, true, e->stream));
+                            (size_t)T * sizeof(int32_t), (size_t)n, hipMemcpyHostToDevice, main_stream(e)));
+    HIPCHK(launch_gram(w, pl, true, main_stream(e)));
     gram_fetch(e, base, pl, n, gram, sums);
     return 0;
 }

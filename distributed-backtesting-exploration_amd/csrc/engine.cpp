@@ -82,7 +82,7 @@ static_assert(kStageAlign == kRowAlign, "batch.h lays staging rows out as the de
 // column; allocates the columns the strategy needs.
 void set_dataset(bt_engine* e, std::vector<SymDesc>&& syms, int64_t rows) {
     // the previous run's top-k chain (second stream) reads the symbol descriptors (ids of its
-    // records), and a column may be reallocated below: both streams drain first (the upload on
+    // records), and a column may be reallocated below: every stream drains first (the upload on
     // the engine stream alone would be ordered after the kernel but not after that chain)
     sync_all(e);
     e->syms = std::move(syms);
@@ -93,7 +93,7 @@ void set_dataset(bt_engine* e, std::vector<SymDesc>&& syms, int64_t rows) {
     e->d_syms.ensure(std::max<size_t>(1, n_sym));
     if (n_sym)
         HIPCHK(hipMemcpyAsync(e->d_syms.p, e->syms.data(), n_sym * sizeof(SymDesc),
-                              hipMemcpyHostToDevice, e->stream));
+                              hipMemcpyHostToDevice, main_stream(e)));
     const size_t r = std::max<int64_t>(1, rows);
     e->d_c.ensure(r);
     if (has_hl(e)) {
@@ -140,40 +140,64 @@ void ensure_outputs(bt_engine* e) {
         e->d_cand.ensure(kTopkCap);
         e->d_top.ensure(kTopkMax + 1);  // [0] = header (record count), then the records
         e->h_top.ensure(kTopkMax + 1);
-        HIPCHK(launch_topk_init(topk_work(e), e->stream));
+        HIPCHK(launch_topk_init(topk_work(e), main_stream(e)));
         e->topk_ready = true;
     }
+}
+
+// Orders the run stream behind what the engine stream holds now, if main_stream() handed it out
+// since the last time.
+void run_stream_follows_main(bt_engine* e) {
+    if (!e->main_dirty || !e->rstream) return;
+    HIPCHK(hipEventRecord(e->ev_main, e->stream));
+    HIPCHK(hipStreamWaitEvent(e->rstream, e->ev_main, 0));
+    e->main_dirty = false;
 }
 
 void run_impl(bt_engine* e) {
     activate(e);
     ensure_outputs(e);
     const int32_t S = (int32_t)e->syms.size();
+    const bool parity = (e->cfg.flags & BT_FLAG_PARITY) != 0;
+    const LaunchPlan pl = plan_launch(e->grid, e->ax[0].data(),
+                                      RunShape{S, e->max_bars, parity, e->seg_req, e->burn_req, e->cus,
+                                               e->stream.owned, e->overlap_on});
     const int64_t run = e->nrun++;
     const int b = (int)(run & 1);
     e->cur = b;
+    const int slot = (int)(run % kNtrRing);
+    if (slot % (kNtrRing / 2) == 0) {
+        // the half ring's last writers ran on either stream and the runs that add into it next
+        // will too: zeroed on the engine stream behind the run stream's last kernel, and the run
+        // stream ordered behind the zeroing at once, not behind this run's kernel. Its last
+        // readers (tstream, 33 or more runs back) ended before the ev_tdone a later run waited for
+        HIPCHK(hipMemsetAsync(e->d_ntr_ring.p + slot, 0, (kNtrRing / 2) * sizeof(unsigned long long),
+                              main_stream(e)));
+        run_stream_follows_main(e);
+    }
+    // A run that may overlap its neighbours (plan.h) goes to the stream of its output buffer: even
+    // runs to the engine stream, odd ones to the run stream, so run i+1's blocks take the slots run
+    // i's last blocks free. Any other run goes to the engine stream behind both streams' kernels,
+    // and the run after it behind it
+    const bool on_run = pl.overlap && b == 1;
+    if (on_run) run_stream_follows_main(e);
+    const hipStream_t st = on_run ? (hipStream_t)e->rstream : pl.overlap ? (hipStream_t)e->stream : main_stream(e);
     // buffer b was last read by the top-k chain / read-back of run i-2: wait for them (no wait
     // packet when they have already finished, the steady state of a pipelined sweep)
     if (e->tdone_armed[b] && hipEventQuery(e->ev_tdone[b]) != hipSuccess)
-        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_tdone[b], 0));
+        HIPCHK(hipStreamWaitEvent(st, e->ev_tdone[b], 0));
     Out out{};
     out.sum = e->d_sum[b].p;
     out.key = e->d_key[b].p;
-    const bool parity = (e->cfg.flags & BT_FLAG_PARITY) != 0;
     out.sums = parity ? e->d_sums.p : nullptr;
     out.trades = parity ? e->d_trades.p : nullptr;
     out.trade_cap = parity ? e->cfg.trade_cap : 0;
-    const int slot = (int)(run % kNtrRing);
-    if (slot % (kNtrRing / 2) == 0)
-        HIPCHK(hipMemsetAsync(e->d_ntr_ring.p + slot, 0, (kNtrRing / 2) * sizeof(unsigned long long),
-                              e->stream));
     e->ntr[b] = e->d_ntr_ring.p + slot;
     out.n_trades = e->ntr[b];
     out.dbg = nullptr;
     if (BT_ABL(e->grid, 64)) {  // profiling stamps (profiling build only)
         e->d_dbg.ensure(kDbgSlots + 8 * kDbgBlocks);
-        HIPCHK(hipMemsetAsync(e->d_dbg.p, 0, (kDbgSlots + 8 * kDbgBlocks) * sizeof(unsigned long long),
-                              e->stream));
+        HIPCHK(hipMemsetAsync(e->d_dbg.p, 0, (kDbgSlots + 8 * kDbgBlocks) * sizeof(unsigned long long), st));
         out.dbg = e->d_dbg.p;
     }
     const bool timing = (e->cfg.flags & BT_FLAG_TIMING) != 0;
@@ -185,10 +209,8 @@ void run_impl(bt_engine* e) {
         }
         ev.first.ensure(0);
         ev.second.ensure(0);
-        HIPCHK(hipEventRecord(ev.first, e->stream));
+        HIPCHK(hipEventRecord(ev.first, st));
     }
-    const LaunchPlan pl = plan_launch(e->grid, e->ax[0].data(),
-                                      RunShape{S, e->max_bars, parity, e->seg_req, e->burn_req, e->cus});
     SegArgs sg{nullptr, nullptr, nullptr, nullptr, pl.G, pl.burn_tiles};
     if (pl.G > 1) {
         e->d_seg.ensure(pl.seg_slots);
@@ -199,34 +221,38 @@ void run_impl(bt_engine* e) {
             sg.ema = e->d_segema.p;
         }
         e->d_refixed.ensure(1);
-        HIPCHK(hipMemsetAsync(e->d_refixed.p, 0, sizeof(unsigned long long), e->stream));
+        HIPCHK(hipMemsetAsync(e->d_refixed.p, 0, sizeof(unsigned long long), st));
         sg.refixed = e->d_refixed.p;
     }
     e->seg_last = pl.G;
     hipError_t err;
     switch (e->cfg.strategy) {
         case BT_SMA_CROSS:
-            err = launch_sma(e->d_syms.p, S, e->d_c.p, e->grid, out, parity, sg, pl, e->stream);
+            err = launch_sma(e->d_syms.p, S, e->d_c.p, e->grid, out, parity, sg, pl, st);
             break;
         case BT_EMA_OLS:
-            err = launch_ema_ols(e->d_syms.p, S, e->d_c.p, e->grid, out, parity, sg, pl, e->stream);
+            err = launch_ema_ols(e->d_syms.p, S, e->d_c.p, e->grid, out, parity, sg, pl, st);
             break;
         default:
             err = launch_boll(e->d_syms.p, S, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, out, parity, sg, pl,
-                              e->stream);
+                              st);
             break;
     }
     HIPCHK(err);
-    hipEvent_t kdone = e->ev_kdone;
+    // the kernel-done event the top-k chain and, for a run on the run stream, the engine stream's
+    // next join wait for: the timing end event when there is one (one marker less between two
+    // runs' kernels; it stays recorded until a drained run's pair is handed out again, and a
+    // drained run has finished)
+    hipEvent_t kdone = e->ev_kdone[on_run];
     if (timing) {
-        HIPCHK(hipEventRecord(ev.second, e->stream));
+        HIPCHK(hipEventRecord(ev.second, st));
         kdone = ev.second;
         e->ev_pending.push_back(std::move(ev));
+    } else if (e->cfg.topk > 0 || on_run) {
+        HIPCHK(hipEventRecord(kdone, st));
     }
+    if (on_run) e->r_last = kdone;
     if (e->cfg.topk > 0) {
-        // the chain waits for the kernel: on the timing end event when there is one (one
-        // marker less between two runs' kernels)
-        if (!timing) HIPCHK(hipEventRecord(kdone, e->stream));
         HIPCHK(hipStreamWaitEvent(e->tstream, kdone, 0));
         HIPCHK(launch_topk(e->d_key[b].p, e->d_sum[b].p, e->d_syms.p, (int64_t)S * e->P, e->P,
                            e->cfg.topk, topk_work(e), e->tstream, pl.topk_lds_free));
@@ -237,13 +263,24 @@ void run_impl(bt_engine* e) {
 }
 
 void drain_timing(bt_engine* e) {
+    // A run counts from its start or from the end of the run before it, whichever is later: on
+    // two streams run i's start event fires while run i-1 still executes, and the start-to-end
+    // intervals of a pipelined loop would add up to more than the time its kernels covered. For
+    // runs a wait apart both give the start-to-end interval.
     for (auto& ev : e->ev_pending) {
         HIPCHK(hipEventSynchronize(ev.second));
+        if (e->r_last == ev.second.ev) e->r_last = nullptr;  // finished: nothing left to join
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
+        if (e->ev_last.second) {
+            float since = 0.f;
+            HIPCHK(hipEventElapsedTime(&since, e->ev_last.second, ev.second));
+            ms = std::min(ms, std::max(since, 0.f));
+            e->ev_pool.push_back(std::move(e->ev_last));
+        }
         e->kernel_ms += ms;
         e->launches += 1;
-        e->ev_pool.push_back(std::move(ev));
+        e->ev_last = std::move(ev);  // its end event stays recorded until the next run is drained
     }
     e->ev_pending.clear();
 }
@@ -284,17 +321,17 @@ void run_batch_impl(bt_engine* e, size_t n, const bt_job_in* jobs, bt_job_out* o
         for (Event& ev : e->ev_batch) ev.ensure(0);
         e->h_sum.ensure(nres);
         set_dataset(e, std::move(syms), rows);
-        HIPCHK(hipEventRecord(e->ev_batch[0], e->stream));
+        HIPCHK(hipEventRecord(e->ev_batch[0], main_stream(e)));
         int32_t* dst[3] = {e->d_c.p, e->d_h.p, e->d_l.p};
         for (int k = 0; k < ncol; ++k)
             HIPCHK(hipMemcpyAsync(dst[k], e->h_stage[k].p, (size_t)rows * 4, hipMemcpyHostToDevice,
-                                  e->stream));
-        HIPCHK(hipEventRecord(e->ev_batch[1], e->stream));
+                                  main_stream(e)));
+        HIPCHK(hipEventRecord(e->ev_batch[1], main_stream(e)));
         run_impl(e);
-        HIPCHK(hipEventRecord(e->ev_batch[2], e->stream));
+        HIPCHK(hipEventRecord(e->ev_batch[2], main_stream(e)));
         HIPCHK(hipMemcpyAsync(e->h_sum.p, e->d_sum[e->cur].p, nres * sizeof(bt_summary),
-                              hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipEventRecord(e->ev_batch[3], e->stream));
+                              hipMemcpyDeviceToHost, main_stream(e)));
+        HIPCHK(hipEventRecord(e->ev_batch[3], main_stream(e)));
         sync_all(e);
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, e->ev_batch[0], e->ev_batch[1]));
@@ -360,8 +397,10 @@ static bt_engine* create_impl(const bt_config* cfg) {
         e->stream.borrow((hipStream_t)cfg->stream);
     else
         e->stream.create();
+    if (e->stream.owned) e->rstream.create();
     e->tstream.create();
-    e->ev_kdone.ensure(hipEventDisableTiming);
+    for (Event& ev : e->ev_kdone) ev.ensure(hipEventDisableTiming);
+    e->ev_main.ensure(hipEventDisableTiming);
     for (Event& ev : e->ev_tdone) ev.ensure(hipEventDisableTiming);
     upload_grid(e.get());
 #ifdef BT_PROFILING
@@ -397,6 +436,14 @@ int32_t bt_set_segments(bt_engine* e, int32_t segments, int32_t burn_tiles) {
     })
 }
 
+int32_t bt_set_run_overlap(bt_engine* e, int32_t on) {
+    ABI_GUARD(-1, {
+        if (!e) throw HipFail{"bt_set_run_overlap: null engine"};
+        e->overlap_on = on != 0;  // the planner reads it per run; any mix of runs stays ordered
+        return 0;
+    })
+}
+
 int32_t bt_last_segments(bt_engine* e, int64_t* refixed_blocks) {
     ABI_GUARD(-1, {
         if (!e) throw HipFail{"null engine"};
@@ -426,7 +473,7 @@ int32_t bt_load_synthetic(bt_engine* e, uint64_t seed, int64_t sym_begin, int32_
         for (int32_t s = 0; s < n_sym; ++s) ids[s] = sym_begin + s;
         layout(e, n_sym, bars.data(), ids.data());
         HIPCHK(launch_gen(e->d_syms.p, n_sym, seed, freq, nullptr, has_hl(e) ? e->d_h.p : nullptr,
-                          has_hl(e) ? e->d_l.p : nullptr, e->d_c.p, e->stream));
+                          has_hl(e) ? e->d_l.p : nullptr, e->d_c.p, main_stream(e)));
         sync_all(e);
         return 0;
     })
@@ -458,7 +505,7 @@ int32_t bt_load_ohlc(bt_engine* e, int32_t n_sym, const int64_t* sym_ids, const 
                 for (int32_t s = 0; s < n_sym; ++s)
                     memcpy(e->h_stage[k].p + e->syms[s].off, src[k] + row_off[s], (size_t)bars[s] * 4);
                 HIPCHK(hipMemcpyAsync(dst[k], e->h_stage[k].p, (size_t)e->rows * 4,
-                                      hipMemcpyHostToDevice, e->stream));
+                                      hipMemcpyHostToDevice, main_stream(e)));
             }
             sync_all(e);
         }

@@ -20,18 +20,29 @@ struct EngineState {
     std::vector<int32_t> ax[4];  // owned copies of the grid axes
     Grid grid{};
     int32_t P = 0;
-    // the engine stream (its own, or bt_config.stream borrowed) and the top-k chain stream (the
-    // chain of run i overlaps the kernel of run i+1). Declared before every buffer and event:
-    // members go in reverse order, so the streams outlive what was enqueued on them
-    Stream tstream, stream;
+    // the engine stream (its own, or bt_config.stream borrowed), the run stream (odd runs that may
+    // overlap their neighbours, plan.h LaunchPlan::overlap; only beside an owned engine stream) and
+    // the top-k chain stream (the chain of run i overlaps the kernel of run i+1). Declared before
+    // every buffer and event: members go in reverse order, so the streams outlive what was
+    // enqueued on them. Only run_impl enqueues on `stream` or `rstream` by name: every other
+    // enqueue asks main_stream() below, which joins the run stream first
+    Stream tstream, rstream, stream;
     // What is still enqueued finishes before the members free what it uses. The engine stream is
     // the first HIP object an engine makes: without it there is nothing to wait for.
     ~EngineState() {
         if (!stream) return;
         (void)hipSetDevice(cfg.device);
         (void)hipStreamSynchronize(stream);
+        if (rstream) (void)hipStreamSynchronize(rstream);
         if (tstream) (void)hipStreamSynchronize(tstream);
     }
+    // The two run streams' ordering against each other (run_impl, main_stream):
+    // r_last: the kernel-done event of the last run on the run stream while the engine stream has
+    // not been ordered behind it (nullptr: nothing to join); main_dirty: the engine stream holds
+    // work, other than overlapping runs, that the run stream has not been ordered behind
+    hipEvent_t r_last = nullptr;
+    bool main_dirty = false;
+    bool overlap_on = true;      // bt_set_run_overlap
     DevBuf<int32_t> d_axes[4];
     DevBuf<int32_t> d_kwin;      // SMA: Grid::kwin, Grid::krecip
     DevBuf<double> d_krecip;
@@ -63,7 +74,8 @@ struct EngineState {
     DevBuf<double> d_segema;
     DevBuf<unsigned long long> d_refixed;
     DevBuf<unsigned long long> d_dbg;
-    Event ev_kdone;      // kernel of the last run finished (main stream)
+    Event ev_kdone[2];   // kernel of the last run on the engine stream [0] / the run stream [1] finished
+    Event ev_main;       // what the engine stream held when the run stream was last ordered behind it
     Event ev_tdone[2];   // readers of buffer b finished (tstream)
     bool tdone_armed[2] = {false, false};
     // top-k work
@@ -77,8 +89,10 @@ struct EngineState {
     bool slot_armed[BT_PIPE_SLOTS] = {};
     bool topk_ready = false;          // top-k buffers allocated and their state initialised
     bool ran = false;
-    // timing of the dominant kernel
+    // timing of the dominant kernel: (start, end) pairs of the runs not yet accounted, spare
+    // pairs, and the last accounted run's pair (its end bounds the next run's time from below)
     std::vector<std::pair<Event, Event>> ev_pending, ev_pool;
+    std::pair<Event, Event> ev_last;
     double kernel_ms = 0.0;
     int64_t launches = 0;
     // bt_run_batch: pinned host staging of the columns in device row layout (c, h, l), the
@@ -92,7 +106,7 @@ struct EngineState {
     // bt_covariance, bt_gram_of)
     // share one device staging arena, grown to the staging_bytes of the current call's plan
     // (plan.h), which lays it out. Sound because every analysis call is synchronous on the engine
-    // stream: it drains both streams on entry and the engine stream before it returns, so no two
+    // stream: it drains every stream on entry and the engine stream before it returns, so no two
     // of them are in flight together and nothing reads the arena between calls.
     DevBuf<uint8_t> d_arena;
     int32_t surface_chunks = 0;    // bt_set_surface_chunks (0 = the planner's choice)
@@ -116,7 +130,22 @@ inline bool has_hl(const bt_engine* e) { return e->cfg.strategy == BT_BOLL; }
 
 inline void sync_all(bt_engine* e) {
     HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->rstream) HIPCHK(hipStreamSynchronize(e->rstream));
+    e->r_last = nullptr;
     if (e->tstream) HIPCHK(hipStreamSynchronize(e->tstream));
+}
+
+// The engine stream for anything but an overlapping run's kernel: loads, read-backs, analysis
+// calls, the counter ring's zeroing, runs that may not overlap. What it enqueues is ordered behind
+// the run stream's last kernel (no wait packet when that kernel has already finished), and the
+// next run on the run stream is ordered behind it (run_impl).
+inline hipStream_t main_stream(bt_engine* e) {
+    if (e->r_last) {
+        if (hipEventQuery(e->r_last) != hipSuccess) HIPCHK(hipStreamWaitEvent(e->stream, e->r_last, 0));
+        e->r_last = nullptr;
+    }
+    e->main_dirty = true;
+    return e->stream;
 }
 
 // The one cast from a staging offset (plan.h Carve) to a typed device pointer.

@@ -45,6 +45,12 @@ struct LaunchPlan {
     size_t pos_off, pos_bytes;     // SMA: SegArgs::pos, in bytes from SegArgs::rec, and its size
     size_t ema_doubles;            // EMA+OLS: doubles of SegArgs::ema
     bool topk_lds_free;            // the top-k chain's histograms must take no LDS
+    // The run may execute beside the run before it and the run after it (consecutive runs on two
+    // streams, engine.cpp run_impl): it touches nothing single-buffered (segment records of a
+    // split run, parity sums and trades, profiling stamps), the engine owns its streams,
+    // bt_set_run_overlap has not switched it off, and it has more blocks than the device holds at
+    // once, so that there is a last round whose freed slots the next run can fill.
+    bool overlap;
 };
 
 struct RunShape {
@@ -52,6 +58,8 @@ struct RunShape {
     bool parity;
     int32_t seg_req, burn_req;     // bt_set_segments: 0 = automatic / default
     int cus;                       // compute units of the device
+    bool own_stream = true;        // the engine made its stream (false: bt_config.stream, the caller's)
+    bool overlap_on = true;        // bt_set_run_overlap
 };
 
 // `ax0`: the host copy of the grid's first axis (Grid::a; the EMA burn-in follows its spans).

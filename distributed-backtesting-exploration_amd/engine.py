@@ -247,6 +247,7 @@ _LATE_SYMBOLS = {
                           C.c_void_p], C.c_int32),
     "bt_gram_of": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
     "bt_set_gram_split": (3, [C.c_void_p, C.c_int32], C.c_int32),
+    "bt_set_run_overlap": (3, [C.c_void_p, C.c_int32], C.c_int32),
     "bt_covariance_host": (3, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                C.c_void_p, C.c_void_p], C.c_int32),
 }
@@ -790,6 +791,12 @@ class Engine:
         """Bar-axis split of the EMA+OLS / Bollinger walks: 0 = automatic, 1 = off, n = n
         segments per symbol; burn_tiles 0 = the strategy's default burn-in."""
         _check(lib().bt_set_segments(self._h, segments, burn_tiles))
+
+    def set_run_overlap(self, on) -> None:
+        """Consecutive runs on two streams in turn, a run's first blocks filling the compute units
+        the run before it frees (bt_set_run_overlap; on by default). Results are identical either
+        way; split runs, parity engines and engines on a caller's stream stay serial."""
+        _check(sym("bt_set_run_overlap")(self._h, 1 if on else 0))
 
     def last_segments(self, with_refixed: bool = False):
         """Segments per symbol of the last run (and, with_refixed, the fix pass's re-walks)."""

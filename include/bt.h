@@ -150,6 +150,16 @@ int32_t bt_num_params(const bt_engine* e);
 int32_t bt_set_segments(bt_engine* e, int32_t segments, int32_t burn_tiles);
 int32_t bt_last_segments(bt_engine* e, int64_t* refixed_blocks);
 
+/* Consecutive bt_run calls of an engine that owns its stream go to two streams in turn, so that a
+ * run's first blocks take the compute units the run before it frees as it drains (on: the
+ * default). A run that is split into bar segments, a parity-mode run, a run whose blocks all fit
+ * on the device at once (nothing queues behind it) and every run of an engine on a caller's stream
+ * (bt_config.stream) never overlap another run, whatever is set here: there the call succeeds and
+ * the engine stays serial. Results are identical either way, and every
+ * other call is ordered behind all earlier runs as before: the records of run i are valid after
+ * its fetch. 0 = off: every run waits for the one before it. */
+int32_t bt_set_run_overlap(bt_engine* e, int32_t on);
+
 /* Phase times of the last bt_run_batch call (host clocks for host phases, HIP events for the
  * device ones). */
 typedef struct bt_batch_profile {
