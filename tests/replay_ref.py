@@ -39,6 +39,29 @@ def curves_from_trades(c, trades):
     return pos, realized + pos.astype(np.int64) * (c - entry)
 
 
+def curves_from_trades_fast(c, trades):
+    """curves_from_trades without a pass over the bars per trade, for series of millions of bars
+    and hundreds of thousands of trades: a trade adds its side and entry price at entry_bar and
+    takes them away at exit_bar, its pnl arrives at exit_bar, and prefix sums of those difference
+    arrays are pos_t, the open trade's entry price and realized_t (the trades of a lane do not
+    overlap; int64 throughout, as the loop). test_gpu_walk_limits.py pins it to the loop."""
+    c = np.asarray(c, np.int64)
+    B = len(c)
+    if trades is None or len(trades) == 0:
+        return np.zeros(B, np.int8), np.zeros(B, np.int64)
+    e, x = trades["entry_bar"].astype(np.int64), trades["exit_bar"].astype(np.int64)
+    side = trades["side"].astype(np.int64)
+    epx, xpx = trades["entry_px"].astype(np.int64), trades["exit_px"].astype(np.int64)
+    d = np.zeros((3, B + 1), np.int64)          # pos, entry price, realized
+    np.add.at(d[0], e, side)
+    np.add.at(d[0], x, -side)
+    np.add.at(d[1], e, epx)
+    np.add.at(d[1], x, -epx)
+    np.add.at(d[2], x, side * (xpx - epx))
+    pos, entry, realized = np.cumsum(d[:, :B], axis=1)
+    return pos.astype(np.int8), realized + pos * (c - entry)
+
+
 def gen_hlc(seed, sym, bars, freq=1):
     """Oracle-generated series of one symbol as (h, l, c)."""
     o, h, lo, c, v = F.gen(seed, sym, bars, freq)
