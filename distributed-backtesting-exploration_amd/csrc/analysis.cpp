@@ -47,14 +47,14 @@ int32_t replay_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade
     std::string why = replay_refusal(!e->syms.empty(), n, trade_cap, trades != nullptr, lanes != nullptr, sum != nullptr);
     if (!why.empty()) refuse(fn, why);
     if (n == 0) return 0;
-    std::vector<ReplayLane> req;
+    std::vector<LaneRef> req;
     int32_t W = 0;  // the longest requested symbol
     why = replay_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, equity || pos, stride, req, W);
     if (!why.empty()) refuse(fn, why);
     const ReplayPlan pl = plan_replay(n, W, trade_cap, stride, equity != nullptr, pos != nullptr);
     uint8_t* base = enter(e, pl.staging_bytes);
     const size_t dcap = (size_t)pl.dcap, pitch = (size_t)pl.pitch;
-    ReplayLane* d_lanes = at<ReplayLane>(base, pl.o_lane);
+    LaneRef* d_lanes = at<LaneRef>(base, pl.o_lane);
     ReplayOut out{};
     out.sum = at<bt_summary>(base, pl.o_sum);
     out.trades = dcap ? at<bt_trade>(base, pl.o_trades) : nullptr;
@@ -74,7 +74,7 @@ int32_t replay_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade
             memset(static_cast<uint8_t*>(dst) + i * dst_pitch + src_pitch, 0, dst_pitch - src_pitch);
     };
     for_chunks((size_t)n, (size_t)pl.lanes_per_chunk, [&](size_t i0, size_t m) {
-        HIPCHK(hipMemcpyAsync(d_lanes, req.data() + i0, m * sizeof(ReplayLane), hipMemcpyHostToDevice, main_stream(e)));
+        HIPCHK(hipMemcpyAsync(d_lanes, req.data() + i0, m * sizeof(LaneRef), hipMemcpyHostToDevice, main_stream(e)));
         if (dcap) HIPCHK(hipMemsetAsync(out.trades, 0, m * dcap * sizeof(bt_trade), main_stream(e)));
         if (equity) HIPCHK(hipMemsetAsync(out.equity, 0, m * pitch * 8, main_stream(e)));
         if (pos) HIPCHK(hipMemsetAsync(out.pos, 0, m * pitch, main_stream(e)));
@@ -325,9 +325,9 @@ int32_t covariance_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t f
     if (!e) refuse(fn, "null engine");
     std::string why = covariance_refusal(!e->syms.empty(), n, lanes != nullptr, from_bar, to_bar, gram || sums || T_out);
     if (!why.empty()) refuse(fn, why);
-    std::vector<ReplayLane> req;
+    std::vector<LaneRef> req;
     int32_t W = 0, T = 0;  // W: the longest requested symbol
-    why = replay_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, false, 0, req, W);
+    why = lanes_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, req, W);
     if (!why.empty()) refuse(fn, why);
     why = covariance_window(from_bar, to_bar, W, T);
     if (!why.empty()) refuse(fn, why);
@@ -341,9 +341,9 @@ int32_t covariance_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t f
         return 0;
     }
     uint8_t* base = enter(e, pl.staging_bytes);
-    ReplayLane* d_lanes = at<ReplayLane>(base, pl.o_lanes);
+    LaneRef* d_lanes = at<LaneRef>(base, pl.o_lanes);
     const GramWork w = gram_work(base, pl, n, T);
-    HIPCHK(hipMemcpyAsync(d_lanes, req.data(), (size_t)n * sizeof(ReplayLane), hipMemcpyHostToDevice, main_stream(e)));
+    HIPCHK(hipMemcpyAsync(d_lanes, req.data(), (size_t)n * sizeof(LaneRef), hipMemcpyHostToDevice, main_stream(e)));
     HIPCHK(hipMemsetAsync(base + pl.o_d, 0, pl.d_bytes, main_stream(e)));
     HIPCHK(launch_gram_walk(d_lanes, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, w, from_bar, from_bar + T, main_stream(e)));
     HIPCHK(launch_gram(w, pl, false, main_stream(e)));

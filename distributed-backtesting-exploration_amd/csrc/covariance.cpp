@@ -109,9 +109,7 @@ int32_t bt_covariance_host(int32_t n, const int64_t* equity, const int32_t* n_ba
                     const int64_t* b = d.data() + (size_t)j * (size_t)T;
                     __int128 v = 0;
                     for (int32_t t = 0; t < T; ++t) v += (__int128)a[t] * (__int128)b[t];
-                    bt_wide x;
-                    x.lo = (uint64_t)v;
-                    x.hi = (int64_t)(uint64_t)((unsigned __int128)v >> 64);
+                    const bt_wide x{bt::wide_lo(v), bt::wide_hi(v)};
                     gram[(size_t)i * (size_t)n + (size_t)j] = x;
                     gram[(size_t)j * (size_t)n + (size_t)i] = x;
                 }

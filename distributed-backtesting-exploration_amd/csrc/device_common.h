@@ -26,7 +26,6 @@ __host__ __device__ inline uint64_t trade_mix_et(uint32_t e, uint32_t t, bool lg
 constexpr int kDstLevels = 6;      // log2(kTile)
 constexpr int kKeyStride = kTile + 1;  // +1 double per key row: conflict-free ds_read_b64
 
-typedef __int128 i128;
 // explicit LDS (address space 3) element types, for pointers kept opaque in a VGPR so that
 // accesses use small immediate offsets from it
 typedef __attribute__((address_space(3))) double lds_f64;

@@ -24,6 +24,8 @@ constexpr int kDbgSlots = 80, kDbgBlocks = 1024;
 
 namespace bt {
 
+typedef __int128 i128;
+
 constexpr int kTile = 64;          // bars per LDS tile (one bit per bar in a 64-bit word)
 constexpr int kRowAlign = 64;      // symbol rows start on 64-element boundaries in HBM
 
@@ -144,15 +146,19 @@ hipError_t launch_boll(const SymDesc* syms, int32_t n_sym, const int32_t* high, 
                        const int32_t* close, const Grid& g, const Out& out, bool parity,
                        const SegArgs& seg, const LaunchPlan& pl, hipStream_t st);
 
-// Replay of chosen lanes (k_replay.hip, bt_replay): one wave64 workgroup per request, which walks
-// the symbol's rows and writes its summary, its first trade_cap trades and, when asked, E_t and
-// pos_t of every bar. The buffers hold one chunk of requests; the host zeroes them before the
-// launch (the kernel writes only trades that happen and bars that exist).
-struct ReplayLane {
+// One (symbol, parameter) lane as the lane kernels (walk_tile.h LaneWalk) take it.
+struct LaneRef {
     int64_t off;                   // SymDesc::off of the lane's symbol
     int32_t bars;
     int32_t param;
 };
+
+using ReplayLane = LaneRef;        // the name the drivers under tests/plan and tests/asan build with
+
+// Replay of chosen lanes (k_replay.hip, bt_replay): one wave64 workgroup per request, which walks
+// the symbol's rows and writes its summary, its first trade_cap trades and, when asked, E_t and
+// pos_t of every bar. The buffers hold one chunk of requests; the host zeroes them before the
+// launch (the kernel writes only trades that happen and bars that exist).
 struct ReplayOut {
     bt_summary* sum;               // [n]
     bt_trade* trades;              // [n * trade_cap], or nullptr with trade_cap 0
@@ -161,7 +167,7 @@ struct ReplayOut {
     int8_t* pos;                   // [n * pitch] or nullptr
     int64_t pitch;                 // elements per curve row, >= the longest requested symbol
 };
-hipError_t launch_replay(const ReplayLane* lanes, int32_t n, const int32_t* high, const int32_t* low,
+hipError_t launch_replay(const LaneRef* lanes, int32_t n, const int32_t* high, const int32_t* low,
                          const int32_t* close, const Grid& g, const ReplayOut& o, hipStream_t st);
 
 // Walk-forward evaluation (k_walkfwd.hip, bt_walk_forward; docs/walkforward_spec.md) of one chunk
@@ -187,10 +193,7 @@ hipError_t launch_wf_select(const WfArgs& a, const Grid& g, const WalkfwdPlan& p
 // accumulators with integer atomics; the finish (one block) folds the replicas into the output
 // rows, scans the equity and writes the summary. The host passes only entries whose clipped
 // window [from, to) is not empty, to <= min(bars, T), and zeroes the accumulators before the walk.
-struct PfLane {
-    int64_t off;                   // SymDesc::off of the entry's symbol
-    int32_t bars;
-    int32_t param;
+struct PfLane : LaneRef {
     int32_t from, to;              // the clipped window
 };
 static_assert(sizeof(PfLane) == 24, "PfLane layout");
@@ -230,7 +233,7 @@ struct GramWork {
     int32_t chunks, chunk_bars;    // bar chunks and the bars of one (a multiple of 64)
 };
 struct GramPlan;
-hipError_t launch_gram_walk(const ReplayLane* lanes, const int32_t* high, const int32_t* low,
+hipError_t launch_gram_walk(const LaneRef* lanes, const int32_t* high, const int32_t* low,
                             const int32_t* close, const Grid& g, const GramWork& w, int32_t from, int32_t to,
                             hipStream_t st);
 // `staged`: D was uploaded (bt_gram_of) and the fold writes the row sums too.
@@ -292,6 +295,14 @@ __host__ __device__ inline uint64_t order_key(double x) {
     return (v.u >> 63) ? ~v.u : (v.u | 0x8000000000000000ULL);
 }
 
+// An int128 as the (lo, hi) words of the ABI's records, and back.
+__host__ __device__ inline i128 wide_join(uint64_t lo, int64_t hi) {
+    return (i128)(((unsigned __int128)(uint64_t)hi << 64) | lo);
+}
+__host__ __device__ inline uint64_t wide_lo(i128 x) { return (uint64_t)x; }
+__host__ __device__ inline int64_t wide_hi(i128 x) { return (int64_t)(x >> 64); }
+__host__ __device__ inline void wide_split(i128 x, uint64_t& lo, int64_t& hi) { lo = wide_lo(x), hi = wide_hi(x); }
+
 // int128 (lo, hi) -> double, round to nearest, ties to even (spec §4 conversion).
 __host__ __device__ inline double i128_to_double(uint64_t lo, int64_t hi) {
     const bool neg = hi < 0;
@@ -352,6 +363,9 @@ __host__ __device__ inline double sharpe_fx(uint64_t s1lo, int64_t s1hi, uint64_
     const double v = ldexp(i128_to_double(s2lo, s2hi), -56) / n - mm;
     return v > 0 ? (m / sqrt(v)) * sqrt_ann : 0.0;
 }
+__host__ __device__ inline double sharpe_fx(i128 s1, i128 s2, int32_t bars, double sqrt_ann) {
+    return sharpe_fx(wide_lo(s1), wide_hi(s1), wide_lo(s2), wide_hi(s2), bars, sqrt_ann);
+}
 
 // Sharpe of a portfolio's per-bar tick increments (docs/portfolio_spec.md §4): the oracle's
 // formula on s1 = sum pnl[t], s2 = sum pnl[t]^2 over the n bars [lo, hi); 0 when there is none.
@@ -363,6 +377,9 @@ __host__ __device__ inline double sharpe_ticks(uint64_t s1lo, int64_t s1hi, uint
     const double mm = m * m;
     const double v = i128_to_double(s2lo, s2hi) / n - mm;
     return v > 0 ? (m / sqrt(v)) * sqrt_ann : 0.0;
+}
+__host__ __device__ inline double sharpe_ticks(i128 s1, i128 s2, int32_t n_bars, double sqrt_ann) {
+    return sharpe_ticks(wide_lo(s1), wide_hi(s1), wide_lo(s2), wide_hi(s2), n_bars, sqrt_ann);
 }
 
 }  // namespace bt

@@ -1,12 +1,9 @@
 // k_gram.hip — covariance of chosen lanes on the device (bt_covariance, bt_gram_of, include/bt.h;
 // semantics: docs/covariance_spec.md).
 //
-// gram_walk_kernel: one wave64 workgroup per lane, walked once over its series in 64-bar tiles with
-// lane = bar (walk_tile.h, the body replay_kernel, wf_walk_kernel and pf_walk_kernel use), from
-// tile 0 (the state needs every bar before the window) to the tile of the window's last bar. Per
-// tile each lane has E_t; E_(t-1) is the lane below's E (the previous tile's last value for lane 0),
-// and the lanes inside the window store d_t = E_t - E_(t-1) as int32 into row i of D at column
-// t - from. The row sum is a carried wave sum, written once. No LDS.
+// gram_walk_kernel: one wave64 workgroup per lane, a LaneWalk (walk_tile.h) from tile 0 to the tile
+// of the window's last bar. The lanes inside the window store their tile's d_t = E_t - E_(t-1) as
+// int32 into row i of D at column t - from. The row sum is a carried wave sum, written once. No LDS.
 //
 // gram_mfma_kernel: D * D^T on v_mfma_f64_16x16x4_f64, one wave per 16 x 16 tile (I <= J) and bar
 // chunk. Every increment is split into two signed 16-bit halves,
@@ -53,40 +50,28 @@ __device__ __forceinline__ void split16(int32_t d, double& h, double& l) {
 
 // STRAT: bt_strategy. Block = one wave; blockIdx.x = the lane's row of D.
 template <int STRAT>
-__global__ __launch_bounds__(64) void gram_walk_kernel(const ReplayLane* __restrict__ lanes,
+__global__ __launch_bounds__(64) void gram_walk_kernel(const LaneRef* __restrict__ lanes,
                                                        const int32_t* __restrict__ high,
                                                        const int32_t* __restrict__ low,
                                                        const int32_t* __restrict__ close, const Grid g,
                                                        const GramWork w, const int32_t from, const int32_t to) {
     const int lane = (int)threadIdx.x;
-    const ReplayLane L = lanes[blockIdx.x];
-    const int32_t B = L.bars;
-    const int32_t last = to < B ? to : B;
+    const LaneRef L = lanes[blockIdx.x];
+    const int32_t last = to < L.bars ? to : L.bars;
     // the lane's bars of the window are [from, end); a symbol that ends before `from` is not walked
     const int32_t end = last > from ? last : 0;
-    const int32_t* __restrict__ cs = close + L.off;
-    const int32_t* __restrict__ hs = STRAT == BT_BOLL ? high + L.off : nullptr;
-    const int32_t* __restrict__ ls = STRAT == BT_BOLL ? low + L.off : nullptr;
-    const LaneParams<STRAT> P(g, L.param);
+    LaneWalk<STRAT> lw(g, L.off, L.bars, L.param, high, low, close, lane);
     int32_t* __restrict__ row = w.D + (int64_t)blockIdx.x * w.pitch;
 
-    WalkState st;
-    int64_t e_prev = 0;              // E of the bar before the tile (E_(-1) = 0)
     int64_t total = 0;               // the row sum so far (wave-uniform)
     // end <= to <= from + T: every column stored to lies inside a row of T
     for (int32_t t0 = 0; t0 < end; t0 += kTile) {
         const int32_t t = t0 + lane;
-        TileLanes o;
-        walk_tile<STRAT>(P, g, st, cs, hs, ls, B, t0, lane, o,
-                         [](int, int32_t, int32_t, int32_t, int64_t, int64_t) {});
-        const int64_t E = o.lreal + (int64_t)o.lpos * ((int64_t)o.c - o.lentry);
-        const int64_t below = __shfl_up((long long)E, 1, 64);
-        const int64_t d = E - (lane == 0 ? e_prev : below);
-        e_prev = lane63_i64(E);
+        const LaneTile o = lw.step(t0);
         if (t0 + kTile <= from) continue;     // nothing is stored before the tile of `from`
         const bool in = t >= from && t < end;
-        if (in) row[t - from] = (int32_t)d;   // |d| < 2^31 (docs/portfolio_spec.md §5)
-        total += wave_sum_i64(in ? d : 0);
+        if (in) row[t - from] = (int32_t)o.d;   // |d| < 2^31 (docs/portfolio_spec.md §5)
+        total += wave_sum_i64(in ? o.d : 0);
     }
     if (lane == 0) w.sums[blockIdx.x] = total;
 }
@@ -141,10 +126,7 @@ __global__ __launch_bounds__(64) void gram_mfma_kernel(const GramWork w) {
     for (int reg = 0; reg < 4; ++reg) {
         const i128 v = (i128)(int64_t)hh[reg] * ((i128)1 << 32) +
                        (i128)((int64_t)hl[reg] + (int64_t)lh[reg]) * ((i128)1 << 16) + (i128)(int64_t)ll[reg];
-        bt_wide x;
-        x.lo = (uint64_t)v;
-        x.hi = (int64_t)(v >> 64);
-        out[(q + 4 * reg) * 16 + r] = x;   // row q + 4 reg of the tile, column r
+        out[(q + 4 * reg) * 16 + r] = bt_wide{wide_lo(v), wide_hi(v)};   // row q + 4 reg of the tile, column r
     }
 }
 
@@ -179,30 +161,19 @@ __global__ __launch_bounds__(kFoldBlock) void gram_fold_kernel(const GramWork w,
     i128 v = 0;
     for (int32_t c = 0; c < w.chunks; ++c) {
         const bt_wide x = p[(int64_t)c * w.tiles * 256];
-        v += (i128)(((unsigned __int128)(uint64_t)x.hi << 64) | x.lo);
+        v += wide_join(x.lo, x.hi);
     }
-    bt_wide x;
-    x.lo = (uint64_t)v;
-    x.hi = (int64_t)(v >> 64);
-    w.gram[at] = x;
+    w.gram[at] = bt_wide{wide_lo(v), wide_hi(v)};
 }
 
-hipError_t launch_gram_walk(const ReplayLane* lanes, const int32_t* high, const int32_t* low,
+hipError_t launch_gram_walk(const LaneRef* lanes, const int32_t* high, const int32_t* low,
                             const int32_t* close, const Grid& g, const GramWork& w, int32_t from, int32_t to,
                             hipStream_t st) {
     if (w.n <= 0) return hipSuccess;
-    const dim3 grid((unsigned)w.n), block(kTile);
-    switch (g.strategy) {
-        case BT_SMA_CROSS:
-            hipLaunchKernelGGL(gram_walk_kernel<BT_SMA_CROSS>, grid, block, 0, st, lanes, high, low, close, g, w, from, to);
-            break;
-        case BT_EMA_OLS:
-            hipLaunchKernelGGL(gram_walk_kernel<BT_EMA_OLS>, grid, block, 0, st, lanes, high, low, close, g, w, from, to);
-            break;
-        default:
-            hipLaunchKernelGGL(gram_walk_kernel<BT_BOLL>, grid, block, 0, st, lanes, high, low, close, g, w, from, to);
-            break;
-    }
+    launch_by_strategy(g.strategy, [&](auto strat) {
+        hipLaunchKernelGGL(gram_walk_kernel<decltype(strat)::value>, dim3((unsigned)w.n), dim3(kTile), 0, st, lanes,
+                           high, low, close, g, w, from, to);
+    });
     return hipGetLastError();
 }
 

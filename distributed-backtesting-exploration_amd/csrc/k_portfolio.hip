@@ -1,13 +1,11 @@
 // k_portfolio.hip — portfolio of chosen lanes on the device (bt_portfolio, include/bt.h; semantics:
 // docs/portfolio_spec.md).
 //
-// pf_walk_kernel: one wave64 workgroup per entry, walked once over its series in 64-bar tiles with
-// lane = bar (walk_tile.h, the body replay_kernel and wf_walk_kernel use), from tile 0 (the state
-// needs every bar before the window) to the tile of the window's last bar. Per tile each lane has
-// E_t and pos_t; E_(t-1) is the lane below's E (the previous tile's last value for lane 0), and the
-// lanes inside the window add E_t - E_(t-1) and their position, as one packed count word, into the
-// per-bar accumulators with no-return 64-bit integer atomics. Integer addition is associative and
-// commutative: the sums do not depend on the order in which the waves arrive. No LDS.
+// pf_walk_kernel: one wave64 workgroup per entry, a LaneWalk (walk_tile.h) from tile 0 to the tile
+// of the window's last bar. The lanes inside the window add their tile's d_t = E_t - E_(t-1) and
+// their position, as one packed count word, into the per-bar accumulators with no-return 64-bit
+// integer atomics. Integer addition is associative and commutative: the sums do not depend on the
+// order in which the waves arrive. No LDS.
 //
 // pf_finish_kernel: one block over [0, T) in block-wide strips. A thread folds the R replicas of
 // its bar and writes pnl, n_long and n_short; the block scans pnl into equity and the equity into
@@ -26,9 +24,9 @@ __device__ __forceinline__ void add_u64(unsigned long long* p, unsigned long lon
 }
 
 __device__ __forceinline__ i128 shfl_down_i128(i128 x, int d) {
-    const uint64_t lo = __shfl_down((unsigned long long)(uint64_t)x, d, 64);
-    const uint64_t hi = __shfl_down((unsigned long long)(uint64_t)((unsigned __int128)x >> 64), d, 64);
-    return (i128)(((unsigned __int128)hi << 64) | lo);
+    const uint64_t lo = __shfl_down((unsigned long long)wide_lo(x), d, 64);
+    const int64_t hi = __shfl_down((long long)wide_hi(x), d, 64);
+    return wide_join(lo, hi);
 }
 
 }  // namespace
@@ -42,34 +40,22 @@ __global__ __launch_bounds__(64) void pf_walk_kernel(const PfLane* __restrict__ 
                                                      const PfWork w) {
     const int lane = (int)threadIdx.x;
     const PfLane L = lanes[blockIdx.x];
-    const int32_t B = L.bars;
-    const int32_t* __restrict__ cs = close + L.off;
-    const int32_t* __restrict__ hs = STRAT == BT_BOLL ? high + L.off : nullptr;
-    const int32_t* __restrict__ ls = STRAT == BT_BOLL ? low + L.off : nullptr;
-    const LaneParams<STRAT> P(g, L.param);
+    LaneWalk<STRAT> lw(g, L.off, L.bars, L.param, high, low, close, lane);
     const int64_t rep = (int64_t)(blockIdx.x % (uint32_t)w.R) * w.pitch;
     unsigned long long* __restrict__ a_pnl = w.acc_pnl + rep;
     unsigned long long* __restrict__ a_cnt = w.acc_cnt + rep;
 
-    WalkState st;
-    int64_t e_prev = 0;              // E of the bar before the tile (E_(-1) = 0)
     // the host clips: from < to <= min(B, T), so every bar added to lies inside a row of T
     for (int32_t t0 = 0; t0 < L.to; t0 += kTile) {
         const int32_t t = t0 + lane;
-        TileLanes o;
-        walk_tile<STRAT>(P, g, st, cs, hs, ls, B, t0, lane, o,
-                         [](int, int32_t, int32_t, int32_t, int64_t, int64_t) {});
-        const int64_t E = o.lreal + (int64_t)o.lpos * ((int64_t)o.c - o.lentry);
-        const int64_t below = __shfl_up((long long)E, 1, 64);
-        const int64_t d = E - (lane == 0 ? e_prev : below);
-        e_prev = lane63_i64(E);
+        const LaneTile o = lw.step(t0);
         if (t0 + kTile <= L.from) continue;   // no atomic before the tile of `from`
         const bool in = t >= L.from && t < L.to;
         const unsigned long long cnt = !in || o.lpos == 0 ? 0ull : o.lpos > 0 ? 1ull : 1ull << 32;
-        const bool add_d = in && d != 0;
+        const bool add_d = in && o.d != 0;
         // warm-up and flat tiles have nothing to add: one wave-uniform test skips both atomics
         if (__ballot(add_d || cnt != 0) == 0) continue;
-        if (add_d) add_u64(a_pnl + t, (unsigned long long)d);
+        if (add_d) add_u64(a_pnl + t, (unsigned long long)o.d);
         if (cnt != 0) add_u64(a_cnt + t, cnt);
     }
 }
@@ -112,7 +98,7 @@ __global__ __launch_bounds__(kFinishWaves * 64) void pf_finish_kernel(const PfWo
         // |pnl[t]| < 2^51 (spec §5): the square through the 64 x 64 -> 128 product
         const uint64_t m = (uint64_t)(p < 0 ? -p : p);
         s1 += (i128)p;
-        s2 += (i128)(((unsigned __int128)__umul64hi(m, m) << 64) | (m * m));
+        s2 += wide_join(m * m, (int64_t)__umul64hi(m, m));
 
         // equity: inclusive scan of pnl over the strip, on top of the carry
         const int64_t in_wave = wave_iscan_i64(p);
@@ -155,10 +141,10 @@ __global__ __launch_bounds__(kFinishWaves * 64) void pf_finish_kernel(const PfWo
         r_mdd[wv] = mdd;
         r_expo[wv] = expo;
         r_gross[wv] = gross;
-        r_s[0][wv] = (uint64_t)s1;
-        r_s[1][wv] = (uint64_t)((unsigned __int128)s1 >> 64);
-        r_s[2][wv] = (uint64_t)s2;
-        r_s[3][wv] = (uint64_t)((unsigned __int128)s2 >> 64);
+        r_s[0][wv] = wide_lo(s1);
+        r_s[1][wv] = (uint64_t)wide_hi(s1);
+        r_s[2][wv] = wide_lo(s2);
+        r_s[3][wv] = (uint64_t)wide_hi(s2);
     }
     __syncthreads();
     if (tid == 0) {
@@ -166,8 +152,8 @@ __global__ __launch_bounds__(kFinishWaves * 64) void pf_finish_kernel(const PfWo
             mdd = max(mdd, r_mdd[i]);
             expo += r_expo[i];
             gross = max(gross, r_gross[i]);
-            s1 += (i128)(((unsigned __int128)r_s[1][i] << 64) | r_s[0][i]);
-            s2 += (i128)(((unsigned __int128)r_s[3][i] << 64) | r_s[2][i]);
+            s1 += wide_join(r_s[0][i], (int64_t)r_s[1][i]);
+            s2 += wide_join(r_s[2][i], (int64_t)r_s[3][i]);
         }
         bt_pf_summary* __restrict__ s = w.sum;
         s->n_lanes = w.n_lanes;
@@ -177,11 +163,9 @@ __global__ __launch_bounds__(kFinishWaves * 64) void pf_finish_kernel(const PfWo
         s->pnl = c_eq;
         s->mdd = mdd;
         s->exposure = expo;
-        s->s1_lo = (uint64_t)s1;
-        s->s1_hi = (int64_t)(s1 >> 64);
-        s->s2_lo = (uint64_t)s2;
-        s->s2_hi = (int64_t)(s2 >> 64);
-        s->sharpe = sharpe_ticks(s->s1_lo, s->s1_hi, s->s2_lo, s->s2_hi, w.hi - w.lo, sqrt_ann);
+        wide_split(s1, s->s1_lo, s->s1_hi);
+        wide_split(s2, s->s2_lo, s->s2_hi);
+        s->sharpe = sharpe_ticks(s1, s2, w.hi - w.lo, sqrt_ann);
     }
 }
 
@@ -189,18 +173,10 @@ hipError_t launch_portfolio(const PfLane* lanes, int32_t n, const int32_t* high,
                             const int32_t* close, const Grid& g, const PfWork& w, const PortfolioPlan& pl,
                             hipStream_t st) {
     if (n > 0) {
-        const dim3 grid((unsigned)n), block(kTile);
-        switch (g.strategy) {
-            case BT_SMA_CROSS:
-                hipLaunchKernelGGL(pf_walk_kernel<BT_SMA_CROSS>, grid, block, 0, st, lanes, high, low, close, g, w);
-                break;
-            case BT_EMA_OLS:
-                hipLaunchKernelGGL(pf_walk_kernel<BT_EMA_OLS>, grid, block, 0, st, lanes, high, low, close, g, w);
-                break;
-            default:
-                hipLaunchKernelGGL(pf_walk_kernel<BT_BOLL>, grid, block, 0, st, lanes, high, low, close, g, w);
-                break;
-        }
+        launch_by_strategy(g.strategy, [&](auto strat) {
+            hipLaunchKernelGGL(pf_walk_kernel<decltype(strat)::value>, dim3((unsigned)n), dim3(kTile), 0, st, lanes,
+                               high, low, close, g, w);
+        });
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }

@@ -889,8 +889,8 @@ __global__ __launch_bounds__(256) void sma_seg_combine(const SymDesc* __restrict
             ntr += r.ntr;
             R += r.R;
             h += r.h;
-            s1 += (i128)(((unsigned __int128)(uint64_t)(int64_t)r.s1hi << 64) | r.s1lo);
-            s2 += (i128)(((unsigned __int128)(uint64_t)(int64_t)r.s2hi << 64) | r.s2lo);
+            s1 += wide_join(r.s1lo, r.s1hi);
+            s2 += wide_join(r.s2lo, r.s2hi);
             if (e0 < 0) e0 = r.e0;
             const Agg a1 = Agg{r.agg1[0], r.agg1[1], r.agg1[2], r.agg1[3]};
             if (pos != 0) {
@@ -923,8 +923,8 @@ __global__ __launch_bounds__(256) void sma_seg_combine(const SymDesc* __restrict
         if (i < n) {
             // bars held: trades are back to back from the first entry to the forced exit at B-1
             const int B = syms[s].bars;
-            write_summary(out, i, ntr, R, mdd, ntr > 0 ? B - 1 - e0 : 0, h, (uint64_t)s1, (int64_t)(s1 >> 64),
-                          (uint64_t)s2, (int64_t)(s2 >> 64), B, sqrt_ann);
+            write_summary(out, i, ntr, R, mdd, ntr > 0 ? B - 1 - e0 : 0, h, wide_lo(s1), wide_hi(s1), wide_lo(s2),
+                          wide_hi(s2), B, sqrt_ann);
         }
     }
     wave_add_trades(out, ntr);

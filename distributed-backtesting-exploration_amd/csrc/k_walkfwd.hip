@@ -2,13 +2,13 @@
 // docs/walkforward_spec.md).
 //
 // wf_walk_kernel: every (row, param) lane of a chunk of dataset rows, one wave64 workgroup each,
-// walked once over its whole series in 64-bar tiles with lane = bar (walk_tile.h, the body
-// replay_kernel uses). On top of a tile's per-lane E_t, pos_(t-1), q_t, q2_t the fold accounting
-// is wave-uniform: for each fold that meets the tile (usually one) a lane mask selects its bars,
-// the Sharpe sums are tile partials in int64 added to int128, exposure and closed trades are
-// popcounts of ballots under the mask, and the fold-local peak and drawdown are prefix maxima
-// relative to E(c_k), which is read by readlane at the boundary or carried from the previous tile.
-// Lane 0 writes a fold's record when its last bar has passed. No LDS.
+// a LaneWalk (walk_tile.h) over its whole series. On top of a tile's per-lane E_t and
+// tile_returns the fold accounting is wave-uniform: for each fold that meets the tile (usually
+// one) a lane mask selects its bars, the Sharpe sums are tile partials in int64 added to int128,
+// exposure and closed trades are popcounts of ballots under the mask, and the fold-local peak and
+// drawdown are a PeakDrawdown under the mask restarted at E(c_k), which is read by readlane at the
+// boundary or carried from the previous tile. Lane 0 writes a fold's record when its last bar has
+// passed. No LDS.
 //
 // wf_select_kernel: one workgroup per (row, step), threads striding over p: each sums its lane's
 // S1/S2 over the training folds in int128, takes sharpe_fx of them, and the block reduces to the
@@ -20,10 +20,6 @@
 namespace bt {
 
 namespace {
-
-__device__ __forceinline__ i128 join128(uint64_t lo, int64_t hi) {
-    return (i128)(((unsigned __int128)(uint64_t)hi << 64) | lo);
-}
 
 // return bars of fold [ck, ck1): t in [max(ck, 1), ck1)
 __device__ __forceinline__ int32_t fold_n_ret(int32_t ck, int32_t ck1) {
@@ -41,13 +37,11 @@ __global__ __launch_bounds__(64) void wf_walk_kernel(const WfArgs a, const int32
     const int lane = (int)threadIdx.x;
     const int32_t row = (int32_t)(blockIdx.x / (uint32_t)a.P), param = (int32_t)(blockIdx.x % (uint32_t)a.P);
     const SymDesc sd = a.syms[row];
-    const int32_t B = sd.bars, K = a.K;
-    const int32_t* __restrict__ cs = close + sd.off;
-    const int32_t* __restrict__ hs = STRAT == BT_BOLL ? high + sd.off : nullptr;
-    const int32_t* __restrict__ ls = STRAT == BT_BOLL ? low + sd.off : nullptr;
+    const LaneRef L{sd.off, sd.bars, param};
+    const int32_t B = L.bars, K = a.K;
     const int32_t* __restrict__ bnd = a.bounds;
     bt_fold* __restrict__ rec = a.rec + ((int64_t)row * K) * a.P + param;   // fold k at rec[k * P]
-    const LaneParams<STRAT> P(g, param);
+    LaneWalk<STRAT> lw(g, L.off, L.bars, L.param, high, low, close, lane);
 
     // empty folds: the staging is zero, only first_bar = c_k is theirs
     for (int32_t k = lane; k < K; k += kTile) {
@@ -55,24 +49,16 @@ __global__ __launch_bounds__(64) void wf_walk_kernel(const WfArgs a, const int32
         if (ck1 <= ck) rec[(int64_t)k * a.P].first_bar = ck;
     }
 
-    // ---- state carried across tiles (wave-uniform): the walk, the open fold k and its sums
-    WalkState st;
+    // ---- carried across tiles (wave-uniform): the open fold k and its sums
     int32_t k = 0, f_expo = 0, f_ntr = 0;
-    int64_t e_prev = 0;              // E of the bar before the tile: E(t0)
-    int64_t f_base = 0, f_peak = 0, f_mdd = 0;
+    int64_t f_base = 0;
+    PeakDrawdown f_pd;
     i128 f_s1 = 0, f_s2 = 0;
 
     for (int32_t t0 = 0; t0 < B && k < K; t0 += kTile) {
-        const int32_t t = t0 + lane;
-        TileLanes w;
-        walk_tile<STRAT>(P, g, st, cs, hs, ls, B, t0, lane, w,
-                         [](int, int32_t, int32_t, int32_t, int64_t, int64_t) {});
-        const int64_t E = w.lreal + (int64_t)w.lpos * ((int64_t)w.c - w.lentry);
-        const bool held = w.valid && t >= 1 && w.lprev != 0;
-        int64_t q, q2;
-        fixed_ret(w.c, w.cp, q, q2);
-        const int64_t r1 = held ? (int64_t)w.lprev * q : 0, r2 = held ? q2 : 0;
-        const uint64_t held_m = __ballot(held);
+        const int64_t e_prev = lw.e_prev;        // E of the bar before the tile: E(t0)
+        const LaneTile w = lw.step(t0);
+        const TileReturns ret = tile_returns(w, t0 + lane);
         const int32_t t1 = min(t0 + kTile, B);   // the tile holds bars [t0, t1)
 
         while (k < K) {
@@ -83,27 +69,21 @@ __global__ __launch_bounds__(64) void wf_walk_kernel(const WfArgs a, const int32
             }
             if (ck >= t1) break;     // starts in a later tile
             if (ck >= t0) {          // starts here: E(c_k) is the bar before it
-                f_base = ck == t0 ? e_prev : lane_i64(E, ck - t0 - 1);
-                f_peak = f_base;
-                f_mdd = 0;
+                f_base = ck == t0 ? e_prev : lane_i64(w.E, ck - t0 - 1);
+                f_pd = PeakDrawdown{f_base, 0};
                 f_expo = f_ntr = 0;
                 f_s1 = f_s2 = 0;
             }
             const int lo = max(ck - t0, 0), hi = min(ck1, t1) - t0;   // its lanes [lo, hi)
             const uint64_t mask = from_bit(lo) & ~from_bit(hi);
             const bool in = (mask >> lane) & 1;
-            // |q|, q2 <= 2^56 (spec §3): a tile's partial sums fit int64
-            f_s1 += (i128)wave_sum_i64(in ? r1 : 0);
-            f_s2 += (i128)wave_sum_i64(in ? r2 : 0);
-            f_expo += __popcll(held_m & mask);
+            f_s1 += (i128)wave_sum_i64(in ? ret.r1 : 0);
+            f_s2 += (i128)wave_sum_i64(in ? ret.r2 : 0);
+            f_expo += __popcll(ret.held & mask);
             f_ntr += __popcll(w.exits & mask);
-            const int64_t pm = wave_maxscan_i64(in ? E : INT64_MIN, lane);
-            const int64_t pk = pm > f_peak ? pm : f_peak;
-            const int64_t dd = lane63_i64(wave_maxscan_i64(in ? pk - E : 0, lane));
-            f_mdd = dd > f_mdd ? dd : f_mdd;
-            f_peak = lane63_i64(pk);
+            f_pd.add(w.E, in, lane);
             if (ck1 > t1) break;     // goes on in the next tile
-            const int64_t e_end = lane_i64(E, ck1 - 1 - t0);
+            const int64_t e_end = lane_i64(w.E, ck1 - 1 - t0);
             if (lane == 0) {
                 bt_fold f;
                 f.first_bar = ck;
@@ -111,18 +91,15 @@ __global__ __launch_bounds__(64) void wf_walk_kernel(const WfArgs a, const int32
                 f.n_trades = f_ntr;
                 f.status = 0;
                 f.pnl = e_end - f_base;
-                f.mdd = f_mdd;
+                f.mdd = f_pd.mdd;
                 f.exposure = f_expo;
-                f.s1_lo = (uint64_t)f_s1;
-                f.s1_hi = (int64_t)(f_s1 >> 64);
-                f.s2_lo = (uint64_t)f_s2;
-                f.s2_hi = (int64_t)(f_s2 >> 64);
-                f.sharpe = sharpe_fx(f.s1_lo, f.s1_hi, f.s2_lo, f.s2_hi, fold_n_ret(ck, ck1) + 1, g.sqrt_ann);
+                wide_split(f_s1, f.s1_lo, f.s1_hi);
+                wide_split(f_s2, f.s2_lo, f.s2_hi);
+                f.sharpe = sharpe_fx(f_s1, f_s2, fold_n_ret(ck, ck1) + 1, g.sqrt_ann);
                 rec[(int64_t)k * a.P] = f;
             }
             ++k;
         }
-        e_prev = lane63_i64(E);
     }
 }
 
@@ -149,11 +126,10 @@ __global__ __launch_bounds__(kSelWaves * 64) void wf_select_kernel(const WfArgs 
             i128 s1 = 0, s2 = 0;
             for (int32_t k = f0; k < j; ++k) {
                 const bt_fold& r = rec[(int64_t)k * P + p];
-                s1 += join128(r.s1_lo, r.s1_hi);
-                s2 += join128(r.s2_lo, r.s2_hi);
+                s1 += wide_join(r.s1_lo, r.s1_hi);
+                s2 += wide_join(r.s2_lo, r.s2_hi);
             }
-            const uint64_t key = order_key(sharpe_fx((uint64_t)s1, (int64_t)(s1 >> 64), (uint64_t)s2,
-                                                     (int64_t)(s2 >> 64), n + 1, sqrt_ann));
+            const uint64_t key = order_key(sharpe_fx(s1, s2, n + 1, sqrt_ann));
             if (key > bk || (key == bk && p < bp)) bk = key, bp = p;
         }
 #pragma unroll
@@ -187,18 +163,10 @@ __global__ __launch_bounds__(kSelWaves * 64) void wf_select_kernel(const WfArgs 
 hipError_t launch_wf_walk(const WfArgs& a, const int32_t* high, const int32_t* low, const int32_t* close,
                           const Grid& g, hipStream_t st) {
     if (a.n_rows <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((int64_t)a.n_rows * a.P)), block(kTile);
-    switch (g.strategy) {
-        case BT_SMA_CROSS:
-            hipLaunchKernelGGL(wf_walk_kernel<BT_SMA_CROSS>, grid, block, 0, st, a, high, low, close, g);
-            break;
-        case BT_EMA_OLS:
-            hipLaunchKernelGGL(wf_walk_kernel<BT_EMA_OLS>, grid, block, 0, st, a, high, low, close, g);
-            break;
-        default:
-            hipLaunchKernelGGL(wf_walk_kernel<BT_BOLL>, grid, block, 0, st, a, high, low, close, g);
-            break;
-    }
+    launch_by_strategy(g.strategy, [&](auto strat) {
+        hipLaunchKernelGGL(wf_walk_kernel<decltype(strat)::value>, dim3((unsigned)((int64_t)a.n_rows * a.P)),
+                           dim3(kTile), 0, st, a, high, low, close, g);
+    });
     return hipGetLastError();
 }
 

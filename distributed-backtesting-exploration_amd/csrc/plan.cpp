@@ -427,7 +427,7 @@ ReplayPlan plan_replay(int32_t n, int32_t W, int32_t trade_cap, int64_t stride, 
     const size_t budget = budget_req > 0 ? budget_req : kReplayBudget;
     pl.dcap = std::max<int64_t>(0, std::min<int64_t>(trade_cap, W));
     pl.pitch = equity || pos ? std::min<int64_t>(stride, align_rows(W)) : 0;
-    const size_t per_lane = sizeof(ReplayLane) + sizeof(bt_summary) + (size_t)pl.dcap * sizeof(bt_trade) +
+    const size_t per_lane = sizeof(LaneRef) + sizeof(bt_summary) + (size_t)pl.dcap * sizeof(bt_trade) +
                             (equity ? (size_t)pl.pitch * 8 : 0) + (pos ? (size_t)pl.pitch : 0);
     // the five regions round up by less than kStagingAlign each: what is left holds whole lanes
     const size_t pad = 5 * kStagingAlign;
@@ -435,7 +435,7 @@ ReplayPlan plan_replay(int32_t n, int32_t W, int32_t trade_cap, int64_t stride, 
     pl.lanes_per_chunk = (int32_t)lanes;
     pl.chunks = lanes ? (int32_t)(((size_t)n + lanes - 1) / lanes) : 0;
     Carve c;
-    pl.o_lane = c.take(lanes * sizeof(ReplayLane));
+    pl.o_lane = c.take(lanes * sizeof(LaneRef));
     pl.o_sum = c.take(lanes * sizeof(bt_summary));
     pl.o_trades = c.take(lanes * (size_t)pl.dcap * sizeof(bt_trade));
     pl.o_equity = c.take(equity ? lanes * (size_t)pl.pitch * 8 : 0);
@@ -535,7 +535,7 @@ GramPlan plan_gram(int32_t n, int32_t T, int cus, int32_t split_req) {
     pl.fold_block = 256;
     pl.fill = (double)pl.tiles * pl.chunks / ((double)std::max(cus, 1) * kGramWavesPerCu);
     Carve c;
-    pl.o_lanes = c.take((size_t)n * sizeof(ReplayLane));
+    pl.o_lanes = c.take((size_t)n * sizeof(LaneRef));
     pl.o_d = c.take((size_t)n * (size_t)pl.pitch * sizeof(int32_t));
     pl.d_bytes = c.end - pl.o_d;
     pl.o_partial = c.take((size_t)pl.chunks * chunk_partial);

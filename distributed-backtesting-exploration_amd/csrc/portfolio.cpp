@@ -49,33 +49,21 @@ std::string PfResolved::count(int32_t from, int32_t to) {
 
 std::string portfolio_resolve(const SymDesc* syms, size_t n_sym, int32_t P, int32_t n, const bt_pf_lane* lanes,
                               int32_t T, PfResolved& out) {
-    const std::unordered_map<int32_t, int32_t> row = symbol_rows(syms, n_sym);
     out = PfResolved{};
     out.req.reserve((size_t)std::max(n, 0));
-    for (int32_t i = 0; i < n; ++i) {
-        const bt_pf_lane& L = lanes[i];
-        const auto it = row.find(L.sym);
-        if (it == row.end())
-            return "unknown symbol id " + std::to_string(L.sym) + " (entry " + std::to_string(i) + ")";
-        if (L.param < 0 || L.param >= P)
-            return "param " + std::to_string(L.param) + " outside [0, " + std::to_string(P) + ") (entry " +
-                   std::to_string(i) + ")";
-        const SymDesc& sd = syms[(size_t)it->second];
+    return resolve_lanes(syms, n_sym, P, n, lanes, "entry", [&](int32_t i, const LaneRef& ref) {
         int32_t from, to;
-        std::string why = portfolio_window(i, L.from_bar, L.to_bar, sd.bars, T, from, to);
-        if (!why.empty()) return why;
-        if (to <= from) continue;
+        std::string why = portfolio_window(i, lanes[i].from_bar, lanes[i].to_bar, ref.bars, T, from, to);
+        if (!why.empty() || to <= from) return why;
         why = out.count(from, to);
-        if (!why.empty()) return why;
-        out.req.push_back(PfLane{sd.off, sd.bars, L.param, from, to});
-    }
-    return "";
+        if (why.empty()) out.req.push_back(PfLane{ref, from, to});
+        return why;
+    });
 }
 
 void portfolio_finish_host(int32_t T, int32_t n_lanes, int32_t lo, int32_t hi, const int64_t* pnl,
                            const int32_t* n_long, const int32_t* n_short, double sqrt_ann, int64_t* equity,
                            bt_pf_summary* sum) {
-    typedef __int128 i128;
     int64_t eq = 0, peak = 0, mdd = 0, expo = 0;
     int32_t gross = 0;
     i128 s1 = 0, s2 = 0;
@@ -101,11 +89,9 @@ void portfolio_finish_host(int32_t T, int32_t n_lanes, int32_t lo, int32_t hi, c
     sum->pnl = eq;
     sum->mdd = mdd;
     sum->exposure = expo;
-    sum->s1_lo = (uint64_t)s1;
-    sum->s1_hi = (int64_t)(uint64_t)((unsigned __int128)s1 >> 64);
-    sum->s2_lo = (uint64_t)s2;
-    sum->s2_hi = (int64_t)(uint64_t)((unsigned __int128)s2 >> 64);
-    sum->sharpe = sharpe_ticks(sum->s1_lo, sum->s1_hi, sum->s2_lo, sum->s2_hi, hi - lo, sqrt_ann);
+    wide_split(s1, sum->s1_lo, sum->s1_hi);
+    wide_split(s2, sum->s2_lo, sum->s2_hi);
+    sum->sharpe = sharpe_ticks(s1, s2, hi - lo, sqrt_ann);
 }
 
 }  // namespace bt

@@ -25,22 +25,27 @@ std::unordered_map<int32_t, int32_t> symbol_rows(const SymDesc* syms, size_t n_s
     return row;
 }
 
-std::string replay_resolve(const SymDesc* syms, size_t n_sym, int32_t P, int32_t n, const bt_lane* lanes,
-                           bool curves, int64_t stride, std::vector<ReplayLane>& req, int32_t& W) {
-    const std::unordered_map<int32_t, int32_t> row = symbol_rows(syms, n_sym);
+std::string lane_refusal(bool unknown, int32_t sym, int32_t param, int32_t P, const char* noun, int64_t i) {
+    const std::string which = std::string(" (") + noun + " " + std::to_string(i) + ")";
+    if (unknown) return "unknown symbol id " + std::to_string(sym) + which;
+    return "param " + std::to_string(param) + " outside [0, " + std::to_string(P) + ")" + which;
+}
+
+std::string lanes_resolve(const SymDesc* syms, size_t n_sym, int32_t P, int32_t n, const bt_lane* lanes,
+                          std::vector<LaneRef>& req, int32_t& W) {
     req.resize((size_t)std::max(n, 0));
     W = 0;
-    for (int32_t i = 0; i < n; ++i) {
-        const auto it = row.find(lanes[i].sym);
-        if (it == row.end())
-            return "unknown symbol id " + std::to_string(lanes[i].sym) + " (lane " + std::to_string(i) + ")";
-        if (lanes[i].param < 0 || lanes[i].param >= P)
-            return "param " + std::to_string(lanes[i].param) + " outside [0, " + std::to_string(P) +
-                   ") (lane " + std::to_string(i) + ")";
-        const SymDesc& sd = syms[(size_t)it->second];
-        req[i] = ReplayLane{sd.off, sd.bars, lanes[i].param};
-        W = std::max(W, sd.bars);
-    }
+    return resolve_lanes(syms, n_sym, P, n, lanes, "lane", [&](int32_t i, const LaneRef& ref) {
+        req[i] = ref;
+        W = std::max(W, ref.bars);
+        return std::string();
+    });
+}
+
+std::string replay_resolve(const SymDesc* syms, size_t n_sym, int32_t P, int32_t n, const bt_lane* lanes,
+                           bool curves, int64_t stride, std::vector<LaneRef>& req, int32_t& W) {
+    const std::string why = lanes_resolve(syms, n_sym, P, n, lanes, req, W);
+    if (!why.empty()) return why;
     if (curves && stride < W)
         return "stride = " + std::to_string(stride) + " shorter than the longest requested symbol (" +
                std::to_string(W) + " bars)";

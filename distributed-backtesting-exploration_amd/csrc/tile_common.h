@@ -477,13 +477,13 @@ __device__ __forceinline__ void seg_fold(const SymDesc* __restrict__ syms, int n
             expo += r.expo;
             R += r.R;
             h += r.h;
-            s1 += (i128)(((unsigned __int128)(uint64_t)r.s1hi << 64) | r.s1lo);
-            s2 += (i128)(((unsigned __int128)(uint64_t)r.s2hi << 64) | r.s2lo);
+            s1 += wide_join(r.s1lo, r.s1hi);
+            s2 += wide_join(r.s2lo, r.s2hi);
             mdd = max(mdd, max(gap + r.C, r.D));
             gap = max(gap + r.A, r.B);
         }
-        write_summary(out, i, ntr, R, mdd, expo, h, (uint64_t)s1, (int64_t)(s1 >> 64), (uint64_t)s2,
-                      (int64_t)(s2 >> 64), syms[s].bars, sqrt_ann);
+        write_summary(out, i, ntr, R, mdd, expo, h, wide_lo(s1), wide_hi(s1), wide_lo(s2), wide_hi(s2),
+                      syms[s].bars, sqrt_ann);
     }
     wave_add_trades(out, ntr);
 }

@@ -1,7 +1,14 @@
-// walk_tile.h — one 64-bar tile of one (symbol, parameter) lane walked by one wave64, lane = bar:
-// the body shared by the lane kernels (k_replay.hip replay_kernel, k_walkfwd.hip wf_walk_kernel).
-// A device implementation of docs/oracle_spec.md §4/§5 beside the sweep kernels (k_sma.hip,
-// k_ema.hip, k_boll.hip).
+// walk_tile.h — what the lane kernels share (k_replay.hip replay_kernel, k_walkfwd.hip
+// wf_walk_kernel, k_portfolio.hip pf_walk_kernel, k_gram.hip gram_walk_kernel): one (symbol,
+// parameter) lane walked by one wave64 workgroup in 64-bar tiles, lane = bar. A device
+// implementation of docs/oracle_spec.md §4/§5 beside the sweep kernels (k_sma.hip, k_ema.hip,
+// k_boll.hip).
+//
+// A lane kernel constructs a LaneWalk<STRAT> from its LaneRef and loops over step(t0) from tile 0
+// (the state needs every bar before those it accounts); step() walks the tile (walk_tile) and
+// gives every lane its bar's position, equity E_t and increment d_t = E_t - E_(t-1). The replay
+// and the walk-forward folds account a tile with tile_returns and a PeakDrawdown under a lane
+// mask, the portfolio and the Gram walk take d_t. launch_by_strategy picks the instantiation.
 //
 // Per tile, data-parallel: coalesced loads of c (h, l for Bollinger) and of the bar that leaves
 // each window (a second coalesced stream at t - w), window sums advanced by wave scans of
@@ -10,8 +17,7 @@
 // only the EMA chain (a 64-step wave-uniform loop, each lane keeping its own bar's value) and the
 // state machine, a wave-uniform loop that advances once per EVENT (entry, exit, flip) and finds
 // the next one with ballots restricted to the lanes after the cursor. Each event updates the
-// per-lane (pos, entry_px, realized) of the lanes at and after it; what a kernel accounts from
-// them (E_t, pos_t, exposure, S1/S2, drawdown) follows lane-parallel in the kernel.
+// per-lane (pos, entry_px, realized) of the lanes at and after it.
 #pragma once
 #include "device_common.h"
 
@@ -27,6 +33,16 @@ __device__ __forceinline__ int64_t lane_i64(int64_t x, int i) {
     const int j = __builtin_amdgcn_readfirstlane(i);
     const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)x, j);
     const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)((uint64_t)x >> 32), j);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// x of the lane below (lane 0: of lane 63). Not __shfl_up(x, 1), whose index is that of the first
+// step of wave_maxscan_i64: sharing it, wf_walk_kernel, which never reads LaneTile::d, kept the
+// six scan indices live across the tile loop (+4 VGPRs).
+__device__ __forceinline__ int64_t lane_below_i64(int64_t x, int lane) {
+    const int src = (lane - 1) << 2;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)x);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)((uint64_t)x >> 32));
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
@@ -264,6 +280,81 @@ __device__ __forceinline__ void walk_tile(const LaneParams<STRAT>& P, const Grid
     o.lentry = lentry;
     o.lreal = lreal;
     o.exits = exits;
+}
+
+// A tile as LaneWalk::step leaves it: walk_tile's lanes and, of the lane's bar t,
+struct LaneTile : TileLanes {
+    int64_t E, d;                    // the equity after it, and E_t - E_(t-1) (E_(-1) = 0)
+};
+
+// A lane being walked: its parameters, its symbol's columns and the state carried across tiles.
+template <int STRAT>
+struct LaneWalk {
+    const Grid& g;
+    const LaneParams<STRAT> P;
+    const int32_t *__restrict__ cs, *__restrict__ hs, *__restrict__ ls;   // hs, ls: null unless Bollinger
+    const int32_t B, lane;
+    WalkState st;
+    int64_t e_prev = 0;              // E of the bar before the next tile (E_(-1) = 0)
+
+    __device__ __forceinline__ LaneWalk(const Grid& g, int64_t off, int32_t bars, int32_t param,
+                                        const int32_t* __restrict__ high, const int32_t* __restrict__ low,
+                                        const int32_t* __restrict__ close, int lane)
+        : g(g), P(g, param), cs(close + off), hs(STRAT == BT_BOLL ? high + off : nullptr),
+          ls(STRAT == BT_BOLL ? low + off : nullptr), B(bars), lane(lane) {}
+
+    // Walks tile [t0, t0 + 64); on_trade as walk_tile takes it.
+    template <class OnTrade>
+    __device__ __forceinline__ LaneTile step(int32_t t0, OnTrade&& on_trade) {
+        LaneTile o;
+        walk_tile<STRAT>(P, g, st, cs, hs, ls, B, t0, lane, o, on_trade);
+        o.E = o.lreal + (int64_t)o.lpos * ((int64_t)o.c - o.lentry);
+        const int64_t below = lane_below_i64(o.E, lane);   // by every lane: lane 1 reads lane 0
+        o.d = o.E - (lane == 0 ? e_prev : below);
+        e_prev = lane63_i64(o.E);
+        return o;
+    }
+    __device__ __forceinline__ LaneTile step(int32_t t0) {
+        return step(t0, [](int, int32_t, int32_t, int32_t, int64_t, int64_t) {});
+    }
+};
+
+// The Sharpe terms of the lane's bar t: r1 = pos_(t-1) q_t and r2 = q2_t where a position was held
+// into the bar, else 0, and the ballot of those lanes. |q|, q2 <= 2^56 (spec §3): a tile's sums
+// of them fit int64.
+struct TileReturns {
+    int64_t r1, r2;
+    uint64_t held;
+};
+__device__ __forceinline__ TileReturns tile_returns(const TileLanes& o, int32_t t) {
+    const bool held = o.valid && t >= 1 && o.lprev != 0;
+    int64_t q, q2;
+    fixed_ret(o.c, o.cp, q, q2);
+    return TileReturns{held ? (int64_t)o.lprev * q : 0, held ? q2 : 0, __ballot(held)};
+}
+
+// Running peak of the equity and the largest drawdown from it (wave-uniform), advanced a tile at
+// a time over the lanes `in`: prefix maxima within the tile on top of the carried peak.
+struct PeakDrawdown {
+    int64_t peak = 0, mdd = 0;
+    __device__ __forceinline__ void add(int64_t E, bool in, int lane) {
+        const int64_t pm = wave_maxscan_i64(in ? E : INT64_MIN, lane);
+        const int64_t pk = pm > peak ? pm : peak;
+        const int64_t dd = lane63_i64(wave_maxscan_i64(in ? pk - E : 0, lane));
+        mdd = dd > mdd ? dd : mdd;
+        peak = lane63_i64(pk);
+    }
+};
+
+// launch(std::integral_constant<int, BT_...>) for the grid's strategy: the one place that turns
+// Grid::strategy into a template argument of a lane kernel.
+template <class F>
+void launch_by_strategy(int32_t strategy, F&& launch) {
+    switch (strategy) {
+        case BT_SMA_CROSS: launch(std::integral_constant<int, BT_SMA_CROSS>{}); break;
+        case BT_EMA_OLS: launch(std::integral_constant<int, BT_EMA_OLS>{}); break;
+        default: launch(std::integral_constant<int, BT_BOLL>{}); break;
+    }
 }
 
 }  // namespace bt

@@ -3,8 +3,9 @@ metadata tests/test_kernel_resources.py checks), its instruction count and a has
 instruction listing (llvm-objdump, without addresses, comments, `<symbol+off>` annotations and
 the zero padding `...` after a section's last kernel). Two builds whose rows agree run the same
 machine code in these kernels: run it on libbt.so and on a reference build (scripts/
-build_ref_lib.sh) and diff the output.
-usage: python scripts/dev/kernel_res.py [path/to/libbt.so]"""
+build_ref_lib.sh) and diff the output. A second argument, a regular expression searched in the
+kernel's symbol name, lists other kernels instead (the lane kernels: 'replay_kernel|wf_|pf_|gram_').
+usage: python scripts/dev/kernel_res.py [path/to/libbt.so [name-regex]]"""
 import hashlib
 import os
 import re
@@ -38,9 +39,10 @@ def listings():
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         T.LIB = sys.argv[1]
+    keep = re.compile(sys.argv[2] if len(sys.argv) > 2 else "tile_kernel|sma|seg_combine")
     lst = listings()
     for name, d in sorted(T._kernels().items()):
-        if "tile_kernel" not in name and "sma" not in name and "seg_combine" not in name:
+        if not keep.search(name):
             continue
         ins = lst.get(name, [])
         print(f"{name[:70]:70s} vgpr {d.get('vgpr_count')} sgpr {d.get('sgpr_count')} "
