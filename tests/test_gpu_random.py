@@ -12,6 +12,7 @@ import pytest
 
 import dbx_amd as D
 from helpers import compare_summary, compare_trades, launch_plan, oracle_row
+from random_cases import _ohlc, _series, _windows
 
 pytestmark = pytest.mark.gpu
 
@@ -20,29 +21,6 @@ CAP = 4096
 # sized so the driver's round-end `-m gpu` run carries a few hundred random cases (~10 s)
 NS = int(os.environ.get("BT_RANDOM_SEEDS", "0"))
 S0 = int(os.environ.get("BT_RANDOM_SEED0", "0"))  # first seed of a deep run (fresh seeds)
-
-
-def _series(rng, n, kind):
-    if kind == "walk":          # ordinary tick walk around $100
-        x = 1_000_000 + np.cumsum(rng.integers(-4000, 4001, n))
-    elif kind == "narrow":      # a few ticks wide: floor keys and exact SMAs collide often
-        x = 10_000 + np.cumsum(rng.integers(-1, 2, n))
-        x = np.clip(x, 10_000, 10_004)
-    elif kind == "plateau":     # long flat stretches with rare jumps
-        x = 20_000 + 50 * np.cumsum(rng.random(n) < 0.03)
-    else:                       # "spiky": near the int32 price ceiling with large moves
-        x = 2_000_000_000 + np.cumsum(rng.integers(-3_000_000, 3_000_001, n))
-    return np.clip(x, 10_000, 2**31 - 1).astype(np.int32)
-
-
-def _ohlc(rng, c):
-    hi = c + rng.integers(0, 3000, len(c)).astype(np.int64)
-    lo = c - rng.integers(0, 3000, len(c)).astype(np.int64)
-    return np.clip(hi, 1, 2**31 - 1).astype(np.int32), np.clip(lo, 1, 2**31 - 1).astype(np.int32)
-
-
-def _windows(rng, k, top):
-    return sorted(set(int(x) for x in rng.integers(1, top, k)))
 
 
 @pytest.mark.parametrize("seed", range(S0, S0 + (NS or 120)))
