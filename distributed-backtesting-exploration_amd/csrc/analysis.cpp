@@ -1,7 +1,7 @@
 // analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of, bt_topk_of,
-// bt_walk_forward, bt_portfolio and bt_covariance / bt_gram_of with their settings. Each call checks
-// its arguments with the pure rules of replay.h / surface.h / topk_rules.h / walkfwd.h / portfolio.h /
-// covariance.h, asks plan.h for its chunks and its staging layout, realises that layout in the
+// bt_walk_forward, bt_trade_stats, bt_portfolio and bt_covariance / bt_gram_of with their settings. Each
+// call checks its arguments with the pure rules of replay.h / surface.h / topk_rules.h / walkfwd.h /
+// tstats.h / portfolio.h / covariance.h, asks plan.h for its chunks and its staging layout, realises that layout in the
 // engine's one arena (engine_state.h), launches, and copies the results back before it returns.
 // Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
 #include <algorithm>
@@ -15,6 +15,7 @@
 #include "replay.h"
 #include "surface.h"
 #include "topk_rules.h"
+#include "tstats.h"
 #include "walkfwd.h"
 
 using namespace bt;
@@ -249,6 +250,58 @@ int32_t walk_forward_impl(bt_engine* e, int32_t K, const int32_t* bounds, int32_
     return 0;
 }
 
+// ---- bt_trade_stats: every lane's, or chosen lanes', trade statistics (k_tstats.hip)
+// The rows (all-lanes mode) or the requests (list mode) go through the device in the chunks of the
+// TstatsPlan: per chunk the walk leaves its records, which are copied out when `out` is given and
+// reduced into agg[P] on the device when `agg` is; agg comes back once, after the last chunk.
+int32_t trade_stats_impl(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstats* out, bt_tstats_agg* agg) {
+    const char* fn = "bt_trade_stats";
+    if (!e) refuse(fn, "null engine");
+    std::string why = tstats_refusal(!e->syms.empty(), n, lanes != nullptr, out != nullptr, agg != nullptr);
+    if (!why.empty()) refuse(fn, why);
+    const bool list = lanes != nullptr;
+    if (list && n == 0) return 0;
+    const int32_t S = (int32_t)e->syms.size(), P = e->P;
+    std::vector<LaneRef> req;
+    if (list) {
+        int32_t W = 0;
+        why = lanes_resolve(e->syms.data(), e->syms.size(), P, n, lanes, req, W);
+        if (!why.empty()) refuse(fn, why);
+    }
+    const TstatsPlan pl = plan_tstats(list ? n : S, P, list, e->cus, e->tstats_budget);
+    if (pl.per_chunk < 1)   // list mode: the record of one lane
+        refuse(fn, tstats_budget_refusal(list ? 1 : P, e->tstats_budget > 0 ? e->tstats_budget : (int64_t)kTstatsBudget));
+    uint8_t* base = enter(e, pl.staging_bytes);
+    TsArgs a{};
+    a.rec = at<bt_tstats>(base, pl.o_rec);
+    a.agg = agg ? at<bt_tstats_agg>(base, pl.o_agg) : nullptr;
+    a.P = P;
+    LaneRef* d_lanes = list ? at<LaneRef>(base, pl.o_lanes) : nullptr;
+    if (agg) HIPCHK(hipMemsetAsync(a.agg, 0, (size_t)P * sizeof(bt_tstats_agg), main_stream(e)));
+    const size_t unit_recs = list ? 1 : (size_t)P;
+    for_chunks(list ? (size_t)n : (size_t)S, (size_t)pl.per_chunk, [&](size_t i0, size_t m) {
+        if (list) {
+            HIPCHK(hipMemcpyAsync(d_lanes, req.data() + i0, m * sizeof(LaneRef), hipMemcpyHostToDevice, main_stream(e)));
+            a.lanes = d_lanes;
+            a.n = (int32_t)m;
+        } else {
+            a.syms = e->d_syms.p + i0;
+            a.n_rows = (int32_t)m;
+        }
+        HIPCHK(launch_tstats_walk(a, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, main_stream(e)));
+        if (agg) HIPCHK(launch_tstats_agg(a, pl, main_stream(e)));
+        if (out)
+            HIPCHK(hipMemcpyAsync(out + i0 * unit_recs, a.rec, m * unit_recs * sizeof(bt_tstats), hipMemcpyDeviceToHost,
+                                  main_stream(e)));
+        HIPCHK(hipStreamSynchronize(main_stream(e)));
+    });
+    if (agg) {
+        HIPCHK(hipMemcpyAsync(agg, a.agg, (size_t)P * sizeof(bt_tstats_agg), hipMemcpyDeviceToHost, main_stream(e)));
+        HIPCHK(hipStreamSynchronize(main_stream(e)));
+    }
+    return 0;
+}
+
 // ---- bt_portfolio: chosen lanes traded together, per bar (k_portfolio.hip)
 // The entries with a non-empty window go up once, the accumulators are zeroed, the walk adds into
 // them and the finish writes the four rows and the summary, which one copy brings back.
@@ -441,6 +494,19 @@ int32_t bt_set_walkfwd_budget(bt_engine* e, int64_t bytes) {
         if (!e) refuse("bt_set_walkfwd_budget", "null engine");
         if (bytes < 0) refuse("bt_set_walkfwd_budget", "bytes = " + std::to_string(bytes) + " is negative");
         e->walkfwd_budget = bytes;
+        return 0;
+    })
+}
+
+int32_t bt_trade_stats(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstats* out, bt_tstats_agg* agg) {
+    ABI_GUARD(-1, { return trade_stats_impl(e, n, lanes, out, agg); })
+}
+
+int32_t bt_set_tstats_budget(bt_engine* e, int64_t bytes) {
+    ABI_GUARD(-1, {
+        if (!e) refuse("bt_set_tstats_budget", "null engine");
+        if (bytes < 0) refuse("bt_set_tstats_budget", "bytes = " + std::to_string(bytes) + " is negative");
+        e->tstats_budget = bytes;
         return 0;
     })
 }

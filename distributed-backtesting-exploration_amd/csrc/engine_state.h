@@ -102,8 +102,8 @@ struct EngineState {
     Event ev_batch[4];
     bt_batch_profile prof{};
     int64_t n_errors = 0;
-    // The analysis calls (analysis.cpp: bt_replay, bt_surface, bt_surface_of, bt_walk_forward, bt_portfolio,
-    // bt_covariance, bt_gram_of)
+    // The analysis calls (analysis.cpp: bt_replay, bt_surface, bt_surface_of, bt_walk_forward, bt_trade_stats,
+    // bt_portfolio, bt_covariance, bt_gram_of)
     // share one device staging arena, grown to the staging_bytes of the current call's plan
     // (plan.h), which lays it out. Sound because every analysis call is synchronous on the engine
     // stream: it drains every stream on entry and the engine stream before it returns, so no two
@@ -112,6 +112,7 @@ struct EngineState {
     int32_t surface_chunks = 0;    // bt_set_surface_chunks (0 = the planner's choice)
     PinnedBuf<uint8_t> h_surface;  // the results of one reduction
     int64_t walkfwd_budget = 0;    // bt_set_walkfwd_budget (0 = kWalkfwdBudget)
+    int64_t tstats_budget = 0;     // bt_set_tstats_budget (0 = kTstatsBudget)
     int32_t portfolio_replicas = 0;  // bt_set_portfolio_replicas (0 = the planner's choice)
     PinnedBuf<uint8_t> h_portfolio;  // the rows and the summary of one portfolio
     int32_t gram_split = 0;          // bt_set_gram_split (0 = the planner's choice)

@@ -188,6 +188,22 @@ hipError_t launch_wf_walk(const WfArgs& a, const int32_t* high, const int32_t* l
                           const Grid& g, hipStream_t st);
 hipError_t launch_wf_select(const WfArgs& a, const Grid& g, const WalkfwdPlan& pl, hipStream_t st);
 
+// Trade statistics (k_tstats.hip, bt_trade_stats; docs/tradestats_spec.md) of one chunk. The walk
+// (one wave64 workgroup per lane) leaves one bt_tstats per lane: with `lanes` the n staged
+// requests in order, else lane row * P + param of the chunk's n_rows dataset rows. The reduction
+// adds a chunk's [n_rows][P] records into agg[P], which the host zeroes before the first chunk.
+struct TsArgs {
+    const SymDesc* syms;           // the chunk's rows (all-lanes mode)
+    const LaneRef* lanes;          // the chunk's requests (list mode), else nullptr
+    bt_tstats* rec;                // [n] or [n_rows][P]
+    bt_tstats_agg* agg;            // [P] (reduction only)
+    int32_t n, n_rows, P;
+};
+struct TstatsPlan;
+hipError_t launch_tstats_walk(const TsArgs& a, const int32_t* high, const int32_t* low, const int32_t* close,
+                              const Grid& g, hipStream_t st);
+hipError_t launch_tstats_agg(const TsArgs& a, const TstatsPlan& pl, hipStream_t st);
+
 // Portfolio of chosen lanes (k_portfolio.hip, bt_portfolio; docs/portfolio_spec.md). The walk (one
 // wave64 workgroup per entry) adds every entry's per-bar pnl and position into replicated per-bar
 // accumulators with integer atomics; the finish (one block) folds the replicas into the output

@@ -474,6 +474,37 @@ WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int 
     return pl;
 }
 
+// --------------------------------------------------------------------------- trade statistics
+TstatsPlan plan_tstats(int32_t units, int32_t P, bool list, int cus, int64_t budget_req) {
+    constexpr int64_t kMaxGrid = 1LL << 30;   // one grid index per lane of a chunk
+    TstatsPlan pl{};
+    units = std::max(units, 0);
+    P = std::max(P, 1);
+    pl.list = list;
+    const size_t budget = budget_req > 0 ? (size_t)budget_req : kTstatsBudget;
+    pl.unit_bytes = list ? sizeof(LaneRef) + sizeof(bt_tstats) : (size_t)P * sizeof(bt_tstats);
+    Carve c;
+    if (list) pl.o_lanes = c.take(0);
+    else pl.o_agg = c.take((size_t)P * sizeof(bt_tstats_agg));
+    // the chunk's regions each round up by less than kStagingAlign
+    const size_t fixed = c.end + (list ? 2 : 1) * kStagingAlign;
+    int64_t per = budget > fixed ? (int64_t)((budget - fixed) / pl.unit_bytes) : 0;
+    per = std::min<int64_t>(per, list ? kMaxGrid : kMaxGrid / P);
+    per = std::min<int64_t>(per, units);
+    pl.per_chunk = (int32_t)per;
+    pl.chunks = per > 0 ? (int32_t)((units + per - 1) / per) : 0;
+    pl.waves = list ? per : per * P;
+    pl.fill = (double)pl.waves / ((double)std::max(cus, 1) * 4 * 8);
+    pl.agg_block = 64 * std::min((P + 63) / 64, 4);
+    pl.agg_pblocks = (P + pl.agg_block - 1) / pl.agg_block;
+    pl.agg_slices = (int32_t)std::min<int64_t>(std::max<int64_t>((per + kTstatsSliceRows - 1) / kTstatsSliceRows, 1),
+                                               kTstatsMaxSlices);
+    if (list) c.take((size_t)per * sizeof(LaneRef));
+    pl.o_rec = c.take((size_t)per * (list ? 1 : (size_t)P) * sizeof(bt_tstats));
+    pl.staging_bytes = per > 0 ? fixed + (size_t)per * pl.unit_bytes : 0;
+    return pl;
+}
+
 // ------------------------------------------------------------------------ portfolio of lanes
 PortfolioPlan plan_portfolio(int32_t n, int32_t T, int cus, int32_t replicas_req, size_t budget_req) {
     PortfolioPlan pl{};

@@ -141,6 +141,30 @@ struct WalkfwdPlan {
 // `budget_req`: bt_set_walkfwd_budget (0 = kWalkfwdBudget).
 WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int cus, int64_t budget_req = 0);
 
+// What the trade statistics (k_tstats.hip, bt_trade_stats) are launched with. The units of a call
+// are dataset rows of P lanes each (all-lanes mode) or requested lanes (list mode), processed in
+// chunks of per_chunk (the last one shorter): chunk c holds units [c * per_chunk, min(units,
+// (c + 1) * per_chunk)), every unit exactly once. A chunk's device staging never exceeds the
+// budget. All-lanes mode: agg[P], which the reduction accumulates across the chunks, then the
+// chunk's records [rows][P]. List mode: the chunk's LaneRef, then its records. per_chunk == 0: one
+// unit alone does not fit, and the call is refused. The reduction runs threads along p in blocks
+// of agg_block, agg_pblocks of them, and cuts a chunk's rows into at most agg_slices slices of at
+// least kTstatsSliceRows rows (grid y), each adding its part into agg with integer atomics.
+constexpr size_t kTstatsBudget = 256u << 20;
+constexpr int32_t kTstatsSliceRows = 64, kTstatsMaxSlices = 64;
+struct TstatsPlan {
+    bool list;
+    int32_t per_chunk, chunks;
+    int64_t waves;                 // walk workgroups (one wave each) of a full chunk
+    double fill;                   // ... in units of what the device holds at once (8 waves per SIMD)
+    int32_t agg_block, agg_pblocks, agg_slices;
+    size_t unit_bytes;             // staging per row (P records) or per lane (LaneRef and record)
+    size_t o_agg, o_lanes, o_rec;  // o_agg: all-lanes mode; o_lanes: list mode
+    size_t staging_bytes;          // of a full chunk (0 with per_chunk == 0)
+};
+// `units`: S in all-lanes mode, n in list mode; `budget_req`: bt_set_tstats_budget (0 = kTstatsBudget).
+TstatsPlan plan_tstats(int32_t units, int32_t P, bool list, int cus, int64_t budget_req = 0);
+
 // What a portfolio (k_portfolio.hip, bt_portfolio) of n entries over T bars is launched with. The
 // walk's workgroups (one wave per entry) add into R replicas of two per-bar accumulators of
 // `pitch` 8-byte words each (entry b uses replica b % R), so that the waves, which all start at

@@ -84,6 +84,25 @@ PF_WHOLE = 2**31 - 1  # to_bar of an entry without a window: every bar of its sy
 WIDE_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<i8")])
 assert WIDE_DTYPE.itemsize == 16
 COV_MAX = 2048  # include/bt.h BT_COV_MAX: lanes per Engine.covariance call
+# include/bt.h bt_tstats and bt_tstats_agg: one lane's trade statistics and drawdown timing, and one
+# parameter's reduced over every dataset row (docs/tradestats_spec.md)
+TSTATS_DTYPE = np.dtype([
+    ("n_trades", "<i4"), ("n_win", "<i4"), ("n_loss", "<i4"), ("status", "<i4"),
+    ("n_long", "<i4"), ("n_long_win", "<i4"), ("max_win_streak", "<i4"), ("max_loss_streak", "<i4"),
+    ("hold_sum", "<i4"), ("hold_win", "<i4"), ("hold_max", "<i4"), ("n_bars", "<i4"),
+    ("gross_win", "<i8"), ("gross_loss", "<i8"), ("max_win", "<i8"), ("max_loss", "<i8"),
+    ("sq_lo", "<u8"), ("sq_hi", "<i8"), ("mdd", "<i8"), ("mdd_bar", "<i4"), ("peak_bar", "<i4"),
+    ("underwater_bars", "<i4"), ("max_underwater", "<i4"), ("hash", "<u8"),
+])
+TSTATS_AGG_DTYPE = np.dtype([
+    ("n_sym", "<i4"), ("n_traded", "<i4"), ("max_win_streak", "<i4"), ("max_loss_streak", "<i4"),
+    ("hold_max", "<i4"), ("max_underwater", "<i4"),
+    ("n_trades", "<i8"), ("n_win", "<i8"), ("n_loss", "<i8"), ("n_long", "<i8"), ("n_long_win", "<i8"),
+    ("hold_sum", "<i8"), ("hold_win", "<i8"), ("gross_win", "<i8"), ("gross_loss", "<i8"),
+    ("max_win", "<i8"), ("max_loss", "<i8"), ("mdd_max", "<i8"), ("sq_lo", "<u8"), ("sq_hi", "<i8"),
+])
+assert TSTATS_DTYPE.itemsize == 128 and TSTATS_AGG_DTYPE.itemsize == 136
+TSTATS_MAX = 1 << 20  # include/bt.h BT_TSTATS_MAX: lanes per Engine.trade_stats call in list mode
 
 
 class BtError(RuntimeError):
@@ -248,6 +267,11 @@ _LATE_SYMBOLS = {
     "bt_gram_of": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
     "bt_set_gram_split": (3, [C.c_void_p, C.c_int32], C.c_int32),
     "bt_set_run_overlap": (3, [C.c_void_p, C.c_int32], C.c_int32),
+    "bt_trade_stats": (3, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_set_tstats_budget": (3, [C.c_void_p, C.c_int64], C.c_int32),
+    "bt_trade_stats_host": (3, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_tstats_agg_host": (3, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_tstats_merge": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], C.c_int32),
     "bt_covariance_host": (3, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                C.c_void_p, C.c_void_p], C.c_int32),
 }
@@ -723,6 +747,128 @@ def covariance_host(equity, n_bars, window=None) -> Covariance:
     return _cov_result(n, wide, sums, T.value)
 
 
+def _ratio(num, den) -> np.ndarray:
+    """num / den in doubles, 0 where den is 0."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    return np.divide(num, den, out=np.zeros(np.broadcast(num, den).shape), where=den != 0)
+
+
+@dataclass
+class TradeStats:
+    """Engine.trade_stats' result (bt_trade_stats, docs/tradestats_spec.md). The derived figures
+    are doubles, each 0 where its denominator is 0, of the per-lane records, or of the
+    per-parameter aggregates with params=True (and when there are no per-lane records)."""
+    lanes: np.ndarray | None      # TSTATS_DTYPE[n] (list mode, request order) or [S, P], when asked for
+    params: np.ndarray | None     # TSTATS_AGG_DTYPE[P], when asked for
+
+    def _of(self, params) -> np.ndarray:
+        r = self.params if params or self.lanes is None else self.lanes
+        if r is None:
+            raise ValueError("trade_stats: that output was not asked for")
+        return r
+
+    @staticmethod
+    def _sq(r) -> np.ndarray:
+        out = np.empty(r.shape, object)
+        flat = out.reshape(-1)
+        for k, (lo, hi) in enumerate(zip(r["sq_lo"].reshape(-1).tolist(), r["sq_hi"].reshape(-1).tolist())):
+            flat[k] = (hi << 64) | lo
+        return out
+
+    @property
+    def sq(self) -> np.ndarray:
+        """The sum of squared trade pnl as Python ints (of the aggregates when there are no
+        per-lane records)."""
+        return self._sq(self._of(False))
+
+    @property
+    def params_sq(self) -> np.ndarray:
+        return self._sq(self._of(True))
+
+    def win_rate(self, params=False) -> np.ndarray:
+        r = self._of(params)
+        return _ratio(r["n_win"], r["n_trades"])
+
+    def profit_factor(self, params=False) -> np.ndarray:
+        r = self._of(params)
+        return _ratio(r["gross_win"], r["gross_loss"])
+
+    def expectancy(self, params=False) -> np.ndarray:
+        """The mean trade pnl, ticks."""
+        r = self._of(params)
+        return _ratio(r["gross_win"] - r["gross_loss"], r["n_trades"])
+
+    def avg_win(self, params=False) -> np.ndarray:
+        r = self._of(params)
+        return _ratio(r["gross_win"], r["n_win"])
+
+    def avg_loss(self, params=False) -> np.ndarray:
+        r = self._of(params)
+        return _ratio(r["gross_loss"], r["n_loss"])
+
+    def payoff(self, params=False) -> np.ndarray:
+        """avg_win over avg_loss."""
+        return _ratio(self.avg_win(params), self.avg_loss(params))
+
+    def avg_hold(self, params=False) -> np.ndarray:
+        """Bars held per trade."""
+        r = self._of(params)
+        return _ratio(r["hold_sum"], r["n_trades"])
+
+    def trade_std(self, params=False) -> np.ndarray:
+        """Population standard deviation of the trade pnl, from sq and the mean."""
+        r = self._of(params)
+        sq = np.array([i128_to_double(int(lo), int(hi)) for lo, hi in
+                       zip(r["sq_lo"].reshape(-1).tolist(), r["sq_hi"].reshape(-1).tolist())], np.float64).reshape(r.shape)
+        return np.sqrt(np.maximum(_ratio(sq, r["n_trades"]) - self.expectancy(params) ** 2, 0.0))
+
+    def t_stat(self, params=False) -> np.ndarray:
+        """expectancy over its standard error trade_std / sqrt(n_trades)."""
+        r = self._of(params)
+        return _ratio(self.expectancy(params) * np.sqrt(r["n_trades"].astype(np.float64)), self.trade_std(params))
+
+
+def trade_stats_host(trades, equity) -> np.ndarray:
+    """bt_trade_stats_host: one lane's TSTATS_DTYPE record (shape ()) from its complete trade list
+    in closing order (TRADE_DTYPE) and its equity curve, one value per bar, on the CPU (no GPU
+    needed): the scalar restatement of Engine.trade_stats."""
+    tr = np.ascontiguousarray(trades if trades is not None else np.zeros(0, TRADE_DTYPE), TRADE_DTYPE).reshape(-1)
+    eq = np.ascontiguousarray(equity, np.int64)
+    if eq.ndim != 1:
+        raise ValueError("equity: one value per bar")
+    out = np.zeros(1, TSTATS_DTYPE)
+    _check(sym("bt_trade_stats_host")(len(tr), tr.ctypes.data if len(tr) else None, len(eq),
+                                      eq.ctypes.data if len(eq) else None, out.ctypes.data))
+    return out[0]
+
+
+def trade_stats_agg_host(recs) -> np.ndarray:
+    """bt_tstats_agg_host: an S x P matrix of TSTATS_DTYPE records reduced over its rows to
+    TSTATS_AGG_DTYPE[P] on the CPU (no GPU needed)."""
+    m = np.ascontiguousarray(recs, TSTATS_DTYPE)
+    if m.ndim != 2:
+        raise ValueError("recs: an S x P array of TSTATS_DTYPE")
+    S, P = m.shape
+    out = np.zeros(max(P, 1), TSTATS_AGG_DTYPE)
+    _check(sym("bt_tstats_agg_host")(S, P, m.ctypes.data if m.size else None, out.ctypes.data))
+    return out[:P]
+
+
+def merge_trade_stats(parts) -> np.ndarray:
+    """bt_tstats_merge: the aggregates (TSTATS_AGG_DTYPE[P], or TradeStats with params) of disjoint
+    row sets (shards, ranks) as one."""
+    parts = [p.params if isinstance(p, TradeStats) else p for p in parts]
+    if not parts or any(p is None for p in parts):
+        raise ValueError("merge_trade_stats: one TSTATS_AGG_DTYPE[P] array per part")
+    P = len(parts[0])
+    if any(len(p) != P for p in parts):
+        raise ValueError("merge_trade_stats: the parts hold different parameter counts")
+    block = np.ascontiguousarray(np.concatenate(parts), TSTATS_AGG_DTYPE)
+    out = np.zeros(max(P, 1), TSTATS_AGG_DTYPE)
+    _check(sym("bt_tstats_merge")(block.ctypes.data, len(parts), P, out.ctypes.data))
+    return out[:P]
+
+
 class Engine:
     """One engine per GPU (one process per GPU)."""
 
@@ -958,6 +1104,36 @@ class Engine:
         """Device staging budget of walk_forward in bytes: 0 = the default (256 MB). Results are
         identical whatever the budget."""
         _check(sym("bt_set_walkfwd_budget")(self._h, nbytes))
+
+    # ---- trade statistics and drawdown timing (bt_trade_stats, k_tstats.hip)
+    def trade_stats(self, lanes=None, per_lane: bool = True, params: bool = False) -> TradeStats:
+        """Per-lane trade statistics of the resident dataset (bt_trade_stats): wins and losses,
+        gross profit and loss, streaks, holding times, the sum of squared trade pnl, and where the
+        largest drawdown began and bottomed and how long the curve stayed under water. With
+        `lanes` (what replay takes; at most TSTATS_MAX) the records of those lanes in request
+        order; without, every lane as an [S, P] matrix (per_lane) and / or one aggregate per
+        parameter over every symbol (params). With per_lane=False nothing of size S x P leaves the
+        device. run() need not have been called."""
+        f = sym("bt_trade_stats")
+        if lanes is not None:
+            if params:
+                raise ValueError("trade_stats: params aggregates every lane of the dataset; leave lanes out")
+            req = as_lanes(lanes)
+            n = len(req)
+            out = np.zeros(max(n, 1), TSTATS_DTYPE)
+            keep = req if n else np.zeros(1, LANE_DTYPE)   # lanes != NULL is what selects list mode
+            _check(f(self._h, n, keep.ctypes.data, out.ctypes.data, None))
+            return TradeStats(out[:n], None)
+        S, P = self.stats()["n_symbols"], self.n_params
+        out = np.zeros(max(S * P, 1), TSTATS_DTYPE) if per_lane else None
+        agg = np.zeros(max(P, 1), TSTATS_AGG_DTYPE) if params else None
+        _check(f(self._h, 0, None, None if out is None else out.ctypes.data, None if agg is None else agg.ctypes.data))
+        return TradeStats(None if out is None else out[:S * P].reshape(S, P), None if agg is None else agg[:P])
+
+    def set_tstats_budget(self, nbytes: int) -> None:
+        """Device staging budget of trade_stats in bytes: 0 = the default (256 MB). Results are
+        identical whatever the budget."""
+        _check(sym("bt_set_tstats_budget")(self._h, nbytes))
 
     # ---- portfolio of chosen lanes (bt_portfolio, k_portfolio.hip)
     def portfolio(self, lanes, windows=None, n_bars=None) -> Portfolio:

@@ -435,6 +435,58 @@ int32_t bt_set_gram_split(bt_engine* e, int32_t k);
  * n_bars[i] bars each, as bt_replay returns them). B_max is the largest n_bars[i]. */
 int32_t bt_covariance_host(int32_t n, const int64_t* equity, const int32_t* n_bars, int64_t stride,
                            int32_t from_bar, int32_t to_bar, bt_wide* gram, int64_t* sums, int32_t* T_out);
+/* ---- per-lane trade statistics and drawdown timing (k_tstats.hip, tstats.cpp; semantics:
+ * docs/tradestats_spec.md). One bt_tstats per (symbol, param) lane, walked once over its whole
+ * series: the counts, sums and extremes of its closed trades (pnl_i = side_i (exit_px_i -
+ * entry_px_i), hold_i = exit_bar_i - entry_bar_i; a win has pnl_i > 0, a loss pnl_i < 0), the
+ * longest runs of wins and of losses, and where the largest drawdown of the equity curve E_t of
+ * spec §4 began and bottomed and how long the curve stayed below its running peak. Every figure is
+ * an integer count, sum or extremum: exact, and independent of every order.
+ *   list mode (lanes != NULL): the n lanes in request order, repeats allowed; bt_lane.sym is the
+ *     global symbol id as in bt_replay. out[n] is required, agg must be NULL; n == 0 returns 0.
+ *   all-lanes mode (lanes == NULL, n == 0): every lane of the resident dataset. out is [S * P]
+ *     row-major or NULL, agg is [P] (one bt_tstats_agg per parameter over every dataset row) or
+ *     NULL, not both NULL. With out == NULL nothing of size S x P leaves the device.
+ * Synchronous like bt_replay: waits for the engine's streams, runs on the engine stream, copies
+ * back; bt_run need not have been called and nothing another entry point reads changes. Device
+ * staging is bounded by a 256 MB budget: rows (all-lanes mode) or lanes (list mode) go through in
+ * chunks. Added within ABI 3 (additive). Returns 0, or -1 with bt_last_error naming the offending
+ * value (the engine stays usable): a null engine, no dataset, n < 0 or n > BT_TSTATS_MAX, n != 0
+ * with lanes == NULL, agg given in list mode, out missing in list mode, both outputs NULL, an
+ * unknown symbol id, param outside [0, P), a budget smaller than one row's P records. */
+typedef struct bt_tstats {            /* 128 bytes */
+    int32_t n_trades, n_win, n_loss, status;        /* flat trades: n_trades - n_win - n_loss; status 0 */
+    int32_t n_long, n_long_win;                     /* trades with side > 0, and the wins among them */
+    int32_t max_win_streak, max_loss_streak;        /* longest runs in closing order; a flat trade ends both */
+    int32_t hold_sum, hold_win, hold_max, n_bars;   /* sum of hold_i, over wins only, the largest; B */
+    int64_t gross_win, gross_loss;                  /* sum of pnl_i over wins; of -pnl_i over losses (>= 0) */
+    int64_t max_win, max_loss;                      /* largest pnl_i; largest -pnl_i over losses; 0 without one */
+    uint64_t sq_lo; int64_t sq_hi;                  /* sum of pnl_i^2, an int128 as in bt_sums */
+    int64_t mdd;                                    /* max over t of peak_t - E_t, peak_t = max(0, E_0..E_t) */
+    int32_t mdd_bar, peak_bar;                      /* first bar at mdd; first bar at that bar's peak; -1, -1 when mdd == 0 */
+    int32_t underwater_bars, max_underwater;        /* bars with E_t < peak_t; the longest run of them */
+    uint64_t hash;                                  /* the trade hash of spec §4 */
+} bt_tstats;
+typedef struct bt_tstats_agg {        /* 136 bytes: one parameter over every dataset row */
+    int32_t n_sym, n_traded;                        /* rows counted; rows with n_trades > 0 */
+    int32_t max_win_streak, max_loss_streak, hold_max, max_underwater;   /* maxima over rows */
+    int64_t n_trades, n_win, n_loss, n_long, n_long_win, hold_sum, hold_win, gross_win, gross_loss;  /* sums */
+    int64_t max_win, max_loss, mdd_max;             /* maxima over rows */
+    uint64_t sq_lo; int64_t sq_hi;                  /* int128 sum */
+} bt_tstats_agg;
+#define BT_TSTATS_MAX (1 << 20)       /* lanes per call in list mode */
+int32_t bt_trade_stats(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstats* out, bt_tstats_agg* agg);
+/* Device staging budget of bt_trade_stats in bytes: 0 = the default (256 MB). Results are
+ * identical whatever the budget. */
+int32_t bt_set_tstats_budget(bt_engine* e, int64_t bytes);
+/* Host, no GPU needed: the scalar restatements. One lane's record from its complete trade list in
+ * closing order and its equity curve (n_bars values, as bt_replay returns them); the reduction of
+ * an S x P record matrix (row-major) to agg[P]; and the merge of `world` aggregates of P records
+ * (in[w * P + p], disjoint row sets; world >= 1) into out[P]. */
+int32_t bt_trade_stats_host(int32_t n_trades, const bt_trade* trades, int32_t n_bars,
+                            const int64_t* equity, bt_tstats* out);
+int32_t bt_tstats_agg_host(int32_t S, int32_t P, const bt_tstats* recs, bt_tstats_agg* agg);
+int32_t bt_tstats_merge(const bt_tstats_agg* in, int32_t world, int32_t P, bt_tstats_agg* out);
 /* Average device time of the dominant kernel (BT_FLAG_TIMING), and how many launches. */
 int32_t bt_kernel_timing(bt_engine* e, double* total_ms, int64_t* launches, const char** name);
 int32_t bt_reset_timing(bt_engine* e);
