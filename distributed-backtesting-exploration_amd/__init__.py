@@ -15,7 +15,8 @@ from .engine import (ABI_VERSION, FOLD_DTYPE, PIPE_SLOTS, WALKFWD_FOLDS_MAX, WF_
                      merge_topk, surface_host, PF_LANE_DTYPE, PF_SUMMARY_DTYPE, PORTFOLIO_MAX, Portfolio, as_pf_lanes,
                      merge_portfolios, portfolio_host, walk_forward_lanes, COV_MAX, WIDE_DTYPE, Covariance,
                      covariance_host, TSTATS_AGG_DTYPE, TSTATS_DTYPE, TSTATS_MAX, TradeStats, merge_trade_stats,
-                     trade_stats_agg_host, trade_stats_host)
+                     trade_stats_agg_host, trade_stats_host, BOOT_GROUP_DTYPE, BOOT_LANE_DTYPE, BOOT_MAX,
+                     BOOT_MAX_RESAMPLES, RealityCheck, reality_check_host)
 
 __all__ = [
     "ABI_VERSION", "FOLD_DTYPE", "PIPE_SLOTS", "WALKFWD_FOLDS_MAX", "WF_STEP_DTYPE", "WalkForward", "walk_forward_host", "BT_BOLL", "BT_DAILY", "BT_EMA_OLS", "BT_FLAG_PARITY", "BT_FLAG_TIMING", "BT_MINUTE",
@@ -25,5 +26,6 @@ __all__ = [
     "merge_topk", "surface_host", "PF_LANE_DTYPE", "PF_SUMMARY_DTYPE", "PORTFOLIO_MAX", "Portfolio", "as_pf_lanes",
     "merge_portfolios", "portfolio_host", "walk_forward_lanes", "COV_MAX", "WIDE_DTYPE", "Covariance",
     "covariance_host", "TSTATS_AGG_DTYPE", "TSTATS_DTYPE", "TSTATS_MAX", "TradeStats", "merge_trade_stats",
-    "trade_stats_agg_host", "trade_stats_host",
+    "trade_stats_agg_host", "trade_stats_host", "BOOT_GROUP_DTYPE", "BOOT_LANE_DTYPE", "BOOT_MAX",
+    "BOOT_MAX_RESAMPLES", "RealityCheck", "reality_check_host",
 ]

@@ -1,7 +1,7 @@
 // analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of, bt_topk_of,
-// bt_walk_forward, bt_trade_stats, bt_portfolio and bt_covariance / bt_gram_of with their settings. Each
+// bt_walk_forward, bt_trade_stats, bt_bootstrap / bt_bootstrap_of, bt_portfolio and bt_covariance / bt_gram_of with their settings. Each
 // call checks its arguments with the pure rules of replay.h / surface.h / topk_rules.h / walkfwd.h /
-// tstats.h / portfolio.h / covariance.h, asks plan.h for its chunks and its staging layout, realises that layout in the
+// tstats.h / bootstrap.h / portfolio.h / covariance.h, asks plan.h for its chunks and its staging layout, realises that layout in the
 // engine's one arena (engine_state.h), launches, and copies the results back before it returns.
 // Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "bootstrap.h"
 #include "covariance.h"
 #include "engine_state.h"
 #include "portfolio.h"
@@ -302,6 +303,120 @@ int32_t trade_stats_impl(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstat
     return 0;
 }
 
+// ---- bt_bootstrap / bt_bootstrap_of: the bootstrap reality check (k_boot.hip)
+// The start table and vmax are made once; the lanes go through the lane kernel in the chunks of the
+// BootPlan (one chunk unless the prefix rows live in the arena or increments are staged); the
+// finish reads every lane's record, which stay in the arena for the whole call, and one copy per
+// output brings the results back.
+struct BootOut {
+    bt_boot_group* groups;
+    bt_boot_lane* lanes;
+    int64_t* vmax;
+    int64_t* boot;
+};
+
+// `req`: the resolved lanes of a list call; `d`: the increments of a staged call; neither: every
+// lane of the dataset, one group per row. `goff`: the groups of a list or staged call (never null
+// there).
+int32_t boot_run(bt_engine* e, const char* fn, int64_t n, int64_t G, const int32_t* goff, const std::vector<LaneRef>* req,
+                 const int32_t* d, int32_t from, int32_t T, int32_t B, int32_t L, uint64_t seed, const BootOut& out) {
+    const bool list = req != nullptr, staged = d != nullptr;
+    const BootPlan pl = plan_boot(n, G, T, B, L, list, staged, out.boot != nullptr, e->cus, e->boot_row, e->boot_budget);
+    std::string why;
+    if (pl.row_refused) why = boot_row_refusal(T, ((size_t)T + 1) * 8, kBootLdsBytes - kBootRedBytes);
+    if (why.empty()) why = boot_budget_refusal(pl.need_bytes, e->boot_budget > 0 ? (size_t)e->boot_budget : kBootBudget);
+    if (!why.empty()) refuse(fn, why);
+    std::vector<int32_t> gid;
+    if (list || staged) {
+        gid.resize((size_t)n);
+        for (int64_t g = 0; g < G; ++g)
+            for (int32_t i = goff[g]; i < goff[g + 1]; ++i) gid[(size_t)i] = (int32_t)g;
+    }
+    uint8_t* base = enter(e, pl.staging_bytes);
+    hipStream_t st = main_stream(e);
+    BootArgs a{};
+    a.syms = e->d_syms.p;
+    a.lanes = list ? at<const LaneRef>(base, pl.o_lanes) : nullptr;
+    a.gid = list || staged ? at<const int32_t>(base, pl.o_gid) : nullptr;
+    a.d = staged ? at<const int32_t>(base, pl.o_d) : nullptr;
+    a.starts = at<const int32_t>(base, pl.o_starts);
+    a.rows = pl.row_mode == 2 ? at<int64_t>(base, pl.o_rows) : nullptr;
+    a.vmax = at<int64_t>(base, pl.o_vmax);
+    a.boot = out.boot ? at<int64_t>(base, pl.o_boot) : nullptr;
+    a.rec = at<bt_boot_lane>(base, pl.o_rec);
+    a.goff = list || staged ? at<const int32_t>(base, pl.o_goff) : nullptr;
+    a.groups = at<bt_boot_group>(base, pl.o_groups);
+    a.pitch = pl.pitch, a.d_pitch = pl.d_pitch;
+    a.P = list || staged ? 1 : e->P;
+    a.G = (int32_t)G;
+    a.from = from, a.T = T, a.B = B, a.Lp = pl.Lp, a.K = pl.K, a.last_len = pl.last_len;
+    if (list || staged) {
+        HIPCHK(hipMemcpyAsync(base + pl.o_goff, goff, ((size_t)G + 1) * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(base + pl.o_gid, gid.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    if (list) HIPCHK(hipMemcpyAsync(base + pl.o_lanes, req->data(), (size_t)n * sizeof(LaneRef), hipMemcpyHostToDevice, st));
+    HIPCHK(launch_boot_starts(a, pl, seed, st));
+    for_chunks((size_t)n, (size_t)pl.per_chunk, [&](size_t i0, size_t m) {
+        a.lane0 = (int64_t)i0;
+        if (staged) {
+            HIPCHK(hipMemcpy2DAsync(base + pl.o_d, (size_t)pl.d_pitch * 4, d + i0 * (size_t)T, (size_t)T * 4, (size_t)T * 4,
+                                    m, hipMemcpyHostToDevice, st));
+            HIPCHK(launch_boot_prefix(a, (int32_t)m, pl, st));   // the next upload is ordered behind it
+        } else {
+            HIPCHK(launch_boot_walk(a, (int32_t)m, pl, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, st));
+        }
+    });
+    if (out.groups) {
+        HIPCHK(launch_boot_finish(a, pl, st));
+        HIPCHK(hipMemcpyAsync(out.groups, a.groups, (size_t)G * sizeof(bt_boot_group), hipMemcpyDeviceToHost, st));
+    }
+    if (out.lanes) HIPCHK(hipMemcpyAsync(out.lanes, a.rec, (size_t)n * sizeof(bt_boot_lane), hipMemcpyDeviceToHost, st));
+    if (out.vmax) HIPCHK(hipMemcpyAsync(out.vmax, a.vmax, (size_t)G * (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    if (out.boot) HIPCHK(hipMemcpyAsync(out.boot, a.boot, (size_t)n * (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int32_t bootstrap_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t G, const int32_t* goff, int32_t from_bar,
+                       int32_t to_bar, int32_t B, int32_t L, uint64_t seed, const BootOut& out) {
+    const char* fn = "bt_bootstrap";
+    const BootCall call{e != nullptr, e && !e->syms.empty(), false, lanes != nullptr, n, G, goff, from_bar, to_bar, B, L,
+                        out.groups || out.lanes || out.vmax || out.boot, out.boot != nullptr};
+    std::string why = boot_refusal(call);
+    if (!why.empty()) refuse(fn, why);
+    int32_t T = 0;
+    if (lanes) {
+        std::vector<LaneRef> req;
+        int32_t W = 0;
+        why = lanes_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, req, W);
+        if (!why.empty()) refuse(fn, why);
+        why = boot_window(from_bar, to_bar, W, T);
+        if (!why.empty()) refuse(fn, why);
+        const int32_t one[2] = {0, n};
+        return boot_run(e, fn, n, goff ? G : 1, goff ? goff : one, &req, nullptr, from_bar, T, B, L, seed, out);
+    }
+    why = boot_window(from_bar, to_bar, e->max_bars, T);
+    if (!why.empty()) refuse(fn, why);
+    const int64_t S = (int64_t)e->syms.size();
+    return boot_run(e, fn, S * e->P, S, nullptr, nullptr, nullptr, from_bar, T, B, L, seed, out);
+}
+
+int32_t bootstrap_of_impl(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t G, const int32_t* goff, int32_t B,
+                          int32_t L, uint64_t seed, const BootOut& out) {
+    const char* fn = "bt_bootstrap_of";
+    const BootCall call{e != nullptr, false, true, d != nullptr, n, G, goff, 0, T, B, L,
+                        out.groups || out.lanes || out.vmax || out.boot, out.boot != nullptr};
+    // T before the rest: a row without bars has no d to ask for
+    int32_t Tw = 0;
+    std::string why = e ? boot_window(0, T, 0, Tw) : "";
+    if (why.empty()) why = boot_refusal(call);
+    if (!why.empty()) refuse(fn, why);
+    why = boot_domain_refusal(n, T, d);
+    if (!why.empty()) refuse(fn, why);
+    const int32_t one[2] = {0, n};
+    return boot_run(e, fn, n, goff ? G : 1, goff ? goff : one, nullptr, d, 0, T, B, L, seed, out);
+}
+
 // ---- bt_portfolio: chosen lanes traded together, per bar (k_portfolio.hip)
 // The entries with a non-empty window go up once, the accumulators are zeroed, the walk adds into
 // them and the finish writes the four rows and the summary, which one copy brings back.
@@ -507,6 +622,41 @@ int32_t bt_set_tstats_budget(bt_engine* e, int64_t bytes) {
         if (!e) refuse("bt_set_tstats_budget", "null engine");
         if (bytes < 0) refuse("bt_set_tstats_budget", "bytes = " + std::to_string(bytes) + " is negative");
         e->tstats_budget = bytes;
+        return 0;
+    })
+}
+
+int32_t bt_bootstrap(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t G, const int32_t* goff, int32_t from_bar,
+                     int32_t to_bar, int32_t B, int32_t L, uint64_t seed, bt_boot_group* groups_out,
+                     bt_boot_lane* lanes_out, int64_t* vmax_out, int64_t* boot_out) {
+    ABI_GUARD(-1, {
+        return bootstrap_impl(e, n, lanes, G, goff, from_bar, to_bar, B, L, seed,
+                              BootOut{groups_out, lanes_out, vmax_out, boot_out});
+    })
+}
+
+int32_t bt_bootstrap_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t G, const int32_t* goff,
+                        int32_t B, int32_t L, uint64_t seed, bt_boot_group* groups_out, bt_boot_lane* lanes_out,
+                        int64_t* vmax_out, int64_t* boot_out) {
+    ABI_GUARD(-1, {
+        return bootstrap_of_impl(e, n, T, d, G, goff, B, L, seed, BootOut{groups_out, lanes_out, vmax_out, boot_out});
+    })
+}
+
+int32_t bt_set_boot_budget(bt_engine* e, int64_t bytes) {
+    ABI_GUARD(-1, {
+        if (!e) refuse("bt_set_boot_budget", "null engine");
+        if (bytes < 0) refuse("bt_set_boot_budget", "bytes = " + std::to_string(bytes) + " is negative");
+        e->boot_budget = bytes;
+        return 0;
+    })
+}
+
+int32_t bt_set_boot_row(bt_engine* e, int32_t mode) {
+    ABI_GUARD(-1, {
+        if (!e) refuse("bt_set_boot_row", "null engine");
+        if (mode < 0 || mode > 2) refuse("bt_set_boot_row", "mode = " + std::to_string(mode) + " outside [0, 2]");
+        e->boot_row = mode;
         return 0;
     })
 }

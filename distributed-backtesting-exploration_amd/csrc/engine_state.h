@@ -103,7 +103,7 @@ struct EngineState {
     bt_batch_profile prof{};
     int64_t n_errors = 0;
     // The analysis calls (analysis.cpp: bt_replay, bt_surface, bt_surface_of, bt_walk_forward, bt_trade_stats,
-    // bt_portfolio, bt_covariance, bt_gram_of)
+    // bt_bootstrap, bt_bootstrap_of, bt_portfolio, bt_covariance, bt_gram_of)
     // share one device staging arena, grown to the staging_bytes of the current call's plan
     // (plan.h), which lays it out. Sound because every analysis call is synchronous on the engine
     // stream: it drains every stream on entry and the engine stream before it returns, so no two
@@ -113,6 +113,8 @@ struct EngineState {
     PinnedBuf<uint8_t> h_surface;  // the results of one reduction
     int64_t walkfwd_budget = 0;    // bt_set_walkfwd_budget (0 = kWalkfwdBudget)
     int64_t tstats_budget = 0;     // bt_set_tstats_budget (0 = kTstatsBudget)
+    int64_t boot_budget = 0;       // bt_set_boot_budget (0 = kBootBudget)
+    int32_t boot_row = 0;          // bt_set_boot_row (0 = the planner's choice, 1 = LDS, 2 = arena)
     int32_t portfolio_replicas = 0;  // bt_set_portfolio_replicas (0 = the planner's choice)
     PinnedBuf<uint8_t> h_portfolio;  // the rows and the summary of one portfolio
     int32_t gram_split = 0;          // bt_set_gram_split (0 = the planner's choice)

@@ -204,6 +204,35 @@ hipError_t launch_tstats_walk(const TsArgs& a, const int32_t* high, const int32_
                               const Grid& g, hipStream_t st);
 hipError_t launch_tstats_agg(const TsArgs& a, const TstatsPlan& pl, hipStream_t st);
 
+// Bootstrap reality check (k_boot.hip, bt_bootstrap / bt_bootstrap_of; docs/bootstrap_spec.md).
+// The start kernel fills the start table and sets vmax to INT64_MIN once per call; the lane kernel
+// (one workgroup per lane of a chunk: lane lane0 + blockIdx.x of the call) builds the lane's prefix
+// row, by a LaneWalk or from staged increments, resamples it and leaves the lane's record, its row
+// of boot and its part of vmax; the finish (one workgroup per group) leaves the group records.
+struct BootArgs {
+    const SymDesc* syms;           // all-lanes mode: the dataset's rows, lane = row * P + param
+    const LaneRef* lanes;          // [n] with a lane list, else nullptr
+    const int32_t* gid;            // [n] every lane's group, or nullptr: lane / P
+    const int32_t* d;              // staged: the chunk's increments [m][d_pitch]
+    const int32_t* starts;         // [K][B]
+    int64_t* rows;                 // the chunk's prefix rows [m][pitch] (arena path), else nullptr
+    int64_t* vmax;                 // [G][B]
+    int64_t* boot;                 // [n][B] or nullptr
+    bt_boot_lane* rec;             // [n]
+    const int32_t* goff;           // [G + 1], or nullptr: g * P
+    bt_boot_group* groups;         // [G]
+    int64_t lane0;                 // the chunk's first lane
+    int64_t pitch, d_pitch;
+    int32_t P, G;
+    int32_t from, T, B, Lp, K, last_len;
+};
+struct BootPlan;
+hipError_t launch_boot_starts(const BootArgs& a, const BootPlan& pl, uint64_t seed, hipStream_t st);
+hipError_t launch_boot_walk(const BootArgs& a, int32_t m, const BootPlan& pl, const int32_t* high, const int32_t* low,
+                            const int32_t* close, const Grid& g, hipStream_t st);
+hipError_t launch_boot_prefix(const BootArgs& a, int32_t m, const BootPlan& pl, hipStream_t st);
+hipError_t launch_boot_finish(const BootArgs& a, const BootPlan& pl, hipStream_t st);
+
 // Portfolio of chosen lanes (k_portfolio.hip, bt_portfolio; docs/portfolio_spec.md). The walk (one
 // wave64 workgroup per entry) adds every entry's per-bar pnl and position into replicated per-bar
 // accumulators with integer atomics; the finish (one block) folds the replicas into the output

@@ -505,6 +505,57 @@ TstatsPlan plan_tstats(int32_t units, int32_t P, bool list, int cus, int64_t bud
     return pl;
 }
 
+// ------------------------------------------------------------------- bootstrap reality check
+BootPlan plan_boot(int64_t n, int64_t G, int32_t T, int32_t B, int32_t L, bool list, bool staged, bool want_boot,
+                   int cus, int32_t row_req, int64_t budget_req) {
+    (void)cus;                                     // one workgroup per lane whatever the device
+    constexpr int64_t kMaxGrid = 1LL << 30;        // one grid index per lane of a chunk
+    BootPlan pl{};
+    n = std::max<int64_t>(n, 1);
+    G = std::max<int64_t>(G, 1);
+    T = std::max(T, 1), B = std::max(B, 1), L = std::max(L, 1);
+    pl.T = T;
+    pl.Lp = std::min(L, T);
+    pl.K = (T + pl.Lp - 1) / pl.Lp;
+    pl.last_len = T - (pl.K - 1) * pl.Lp;
+    const size_t row_bytes = ((size_t)T + 1) * 8;
+    const bool fits = kBootRedBytes + row_bytes <= kBootLdsBytes;
+    pl.row_refused = row_req == 1 && !fits;
+    pl.row_mode = row_req == 2 || !fits ? 2 : 1;
+    pl.waves = std::min(std::max(kBootWaves, 1), kBootMaxWaves);
+    pl.block = 64 * pl.waves;
+    pl.lds_bytes = kBootRedBytes + (pl.row_mode == 1 ? row_bytes : 0);
+    pl.pitch = pl.row_mode == 2 ? ((int64_t)T + 1 + 31) / 32 * 32 : 0;   // rows of whole 256-byte lines
+    pl.d_pitch = staged ? ((int64_t)T + 63) / 64 * 64 : 0;
+    pl.starts_block = 256;
+    pl.starts_blocks = ((int64_t)pl.K * B + pl.starts_block - 1) / pl.starts_block;
+    pl.finish_block = 256;
+    const size_t budget = budget_req > 0 ? (size_t)budget_req : kBootBudget;
+    Carve c;
+    pl.o_starts = c.take((size_t)pl.K * (size_t)B * 4);
+    pl.o_goff = c.take(((size_t)G + 1) * 4);
+    pl.o_vmax = c.take((size_t)G * (size_t)B * 8);
+    pl.o_groups = c.take((size_t)G * sizeof(bt_boot_group));
+    pl.o_rec = c.take((size_t)n * sizeof(bt_boot_lane));
+    pl.o_boot = c.take(want_boot ? (size_t)n * (size_t)B * 8 : 0);
+    pl.o_lanes = c.take(list ? (size_t)n * sizeof(LaneRef) : 0);
+    pl.o_gid = c.take(list || staged ? (size_t)n * 4 : 0);
+    // the chunk's regions: whole 256-byte lines per lane, so they round up by nothing
+    pl.unit_bytes = (size_t)pl.pitch * 8 + (size_t)pl.d_pitch * 4;
+    const size_t fixed = c.end;
+    pl.need_bytes = std::max(fixed + pl.unit_bytes, kStagingAlign);
+    int64_t per = n;
+    if (pl.need_bytes > budget) per = 0;
+    else if (pl.unit_bytes > 0) per = std::min<int64_t>(n, (int64_t)((budget - fixed) / pl.unit_bytes));
+    per = std::min(per, kMaxGrid);
+    pl.per_chunk = (int32_t)per;
+    pl.chunks = per > 0 ? (int32_t)((n + per - 1) / per) : 0;
+    pl.o_rows = c.take((size_t)per * (size_t)pl.pitch * 8);
+    pl.o_d = c.take((size_t)per * (size_t)pl.d_pitch * 4);
+    pl.staging_bytes = per > 0 ? c.staging_bytes() : 0;
+    return pl;
+}
+
 // ------------------------------------------------------------------------ portfolio of lanes
 PortfolioPlan plan_portfolio(int32_t n, int32_t T, int cus, int32_t replicas_req, size_t budget_req) {
     PortfolioPlan pl{};

@@ -165,6 +165,49 @@ struct TstatsPlan {
 // `units`: S in all-lanes mode, n in list mode; `budget_req`: bt_set_tstats_budget (0 = kTstatsBudget).
 TstatsPlan plan_tstats(int32_t units, int32_t P, bool list, int cus, int64_t budget_req = 0);
 
+// What a bootstrap reality check (k_boot.hip, bt_bootstrap / bt_bootstrap_of) of n lanes in G
+// groups over T bars, B resamples in blocks of L bars, is launched with. Blocks: Lp = min(L, T),
+// K = ceil(T / Lp) per resample, the last one of last_len bars. A lane's prefix row of T + 1 words
+// lives in LDS (row_mode 1) while kBootRedBytes + (T + 1) * 8 fit kBootLdsBytes, else in the
+// staging arena (row_mode 2), in rows of `pitch` words. One workgroup of `waves` waves per lane: one
+// wave walks, all of them resample (thread = resample). Held for the whole call: the start table
+// [K][B] int32, the group offsets, vmax [G][B], the group records, the lane records [n], a requested
+// boot [n][B] and, with a lane list, the LaneRefs and every lane's group. Per chunk of per_chunk
+// lanes (the last one shorter; chunk c holds lanes [c * per_chunk, min(n, (c + 1) * per_chunk)),
+// every lane exactly once): the arena rows and a staged call's increments [per_chunk][d_pitch]
+// int32. The whole never exceeds the budget; need_bytes is the staging of a call with one lane per
+// chunk, and per_chunk == 0 says that even that does not fit (the call is refused with need_bytes
+// named). row_refused: mode 1 was asked for and the row does not fit.
+constexpr size_t kBootBudget = 256u << 20;
+constexpr size_t kBootLdsBytes = 64 * 1024;    // dynamic LDS of a workgroup, reduction scratch included
+constexpr size_t kBootRedBytes = 512;          // the workgroup's reduction scratch, in front of the row
+#ifndef BT_BOOT_WAVES
+#define BT_BOOT_WAVES 4                        // measured: DESIGN.md §4.11
+#endif
+constexpr int32_t kBootWaves = BT_BOOT_WAVES;
+constexpr int32_t kBootMaxWaves = 4;
+struct BootPlan {
+    int32_t T, Lp, K, last_len;
+    int32_t row_mode;              // 1 = LDS, 2 = arena
+    bool row_refused;
+    int32_t waves, block;          // of the lane workgroup
+    size_t lds_bytes;              // its dynamic LDS
+    int64_t pitch, d_pitch;        // words per arena row (0 in LDS mode); int32 per staged d row (0 unless staged)
+    int32_t per_chunk, chunks;
+    int32_t starts_block;          // threads of a start-table block
+    int64_t starts_blocks;
+    int32_t finish_block;          // threads of a finish block (one block per group)
+    size_t o_starts, o_goff, o_vmax, o_groups, o_rec, o_boot, o_lanes, o_gid, o_rows, o_d;
+    size_t unit_bytes;             // per lane of a chunk
+    size_t need_bytes;
+    size_t staging_bytes;          // of a full chunk (0 with per_chunk == 0)
+};
+// `list`: the call has a lane list (LaneRefs and group ids are staged); `staged`: bt_bootstrap_of
+// (group ids and d are staged); neither: all-lanes mode, groups of P lanes. `row_req`:
+// bt_set_boot_row; `budget_req`: bt_set_boot_budget (0 = kBootBudget).
+BootPlan plan_boot(int64_t n, int64_t G, int32_t T, int32_t B, int32_t L, bool list, bool staged, bool want_boot,
+                   int cus, int32_t row_req = 0, int64_t budget_req = 0);
+
 // What a portfolio (k_portfolio.hip, bt_portfolio) of n entries over T bars is launched with. The
 // walk's workgroups (one wave per entry) add into R replicas of two per-bar accumulators of
 // `pitch` 8-byte words each (entry b uses replica b % R), so that the waves, which all start at

@@ -103,6 +103,14 @@ TSTATS_AGG_DTYPE = np.dtype([
 ])
 assert TSTATS_DTYPE.itemsize == 128 and TSTATS_AGG_DTYPE.itemsize == 136
 TSTATS_MAX = 1 << 20  # include/bt.h BT_TSTATS_MAX: lanes per Engine.trade_stats call in list mode
+# include/bt.h bt_boot_lane and bt_boot_group: one lane's and one group's result of the bootstrap
+# reality check (docs/bootstrap_spec.md); m1 and m2 are int128 as lo/hi words
+BOOT_LANE_DTYPE = np.dtype([("sum", "<i8"), ("n_nonpos", "<i8"), ("m1_lo", "<u8"), ("m1_hi", "<i8"),
+                            ("m2_lo", "<u8"), ("m2_hi", "<i8")])
+BOOT_GROUP_DTYPE = np.dtype([("best_sum", "<i8"), ("best_lane", "<i4"), ("n_lanes", "<i4"), ("n_ge", "<i8")])
+assert BOOT_LANE_DTYPE.itemsize == 48 and BOOT_GROUP_DTYPE.itemsize == 24
+BOOT_MAX = 1 << 20  # include/bt.h BT_BOOT_MAX: lanes per call with a lane list, and of bootstrap_of
+BOOT_MAX_RESAMPLES = 65536  # include/bt.h BT_BOOT_MAX_RESAMPLES
 
 
 class BtError(RuntimeError):
@@ -272,6 +280,15 @@ _LATE_SYMBOLS = {
     "bt_trade_stats_host": (3, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
     "bt_tstats_agg_host": (3, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32),
     "bt_tstats_merge": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], C.c_int32),
+    "bt_bootstrap": (3, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                         C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_bootstrap_of": (3, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                            C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_set_boot_budget": (3, [C.c_void_p, C.c_int64], C.c_int32),
+    "bt_set_boot_row": (3, [C.c_void_p, C.c_int32], C.c_int32),
+    "bt_bootstrap_host": (3, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                              C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p], C.c_int32),
     "bt_covariance_host": (3, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                C.c_void_p, C.c_void_p], C.c_int32),
 }
@@ -747,6 +764,101 @@ def covariance_host(equity, n_bars, window=None) -> Covariance:
     return _cov_result(n, wide, sums, T.value)
 
 
+def _wide_ints(lo, hi) -> list:
+    return [(h << 64) | l for l, h in zip(lo.reshape(-1).tolist(), hi.reshape(-1).tolist())]
+
+
+@dataclass
+class RealityCheck:
+    """Engine.reality_check's result (bt_bootstrap, docs/bootstrap_spec.md): White's bootstrap
+    reality check of the best lane of every group, over `resamples` circular block resamples of the
+    lanes' per-bar pnl increments. Every stored figure is an exact integer."""
+    groups: np.ndarray            # BOOT_GROUP_DTYPE[G]
+    resamples: int                # B
+    lanes: np.ndarray | None      # BOOT_LANE_DTYPE[n] (per_lane)
+    vmax: np.ndarray | None       # int64[G, B]: V* of every group and resample (vmax)
+    boot: np.ndarray | None       # int64[n, B]: the raw resampled sums (boot)
+
+    def p_value(self) -> np.ndarray:
+        """n_ge / B per group: how often the best centred resampled sum of the group reaches the
+        observed best sum."""
+        return self.groups["n_ge"].astype(np.float64) / float(self.resamples)
+
+    def critical(self, q: float) -> np.ndarray:
+        """Per group the smallest observed-best sum that would have had a p-value of at most
+        1 - q: the ceil(q B)-th smallest V*, plus one tick (int64)."""
+        if self.vmax is None:
+            raise ValueError("reality_check: vmax was not asked for")
+        if not 0.0 < q <= 1.0:
+            raise ValueError("critical: q in (0, 1]")
+        k = max(int(np.ceil(q * self.resamples)), 1)
+        return np.sort(self.vmax, axis=1)[:, k - 1] + 1
+
+    def _lanes(self) -> np.ndarray:
+        if self.lanes is None:
+            raise ValueError("reality_check: per_lane was not asked for")
+        return self.lanes
+
+    def lane_se(self) -> np.ndarray:
+        """The bootstrap standard error of every lane's sum: the root of m2 / B - (m1 / B)^2,
+        formed exactly as (B m2 - m1^2) / B^2 in Python ints and then rounded once."""
+        r, B = self._lanes(), self.resamples
+        m1, m2 = _wide_ints(r["m1_lo"], r["m1_hi"]), _wide_ints(r["m2_lo"], r["m2_hi"])
+        var = [B * b - a * a for a, b in zip(m1, m2)]
+        return np.array([float(np.sqrt(v / (B * B))) if v > 0 else 0.0 for v in var], np.float64).reshape(r.shape)
+
+    def lane_p(self) -> np.ndarray:
+        """n_nonpos / B per lane: how often a lane's resampled sum is not positive."""
+        return self._lanes()["n_nonpos"].astype(np.float64) / float(self.resamples)
+
+
+def _as_goff(groups, n):
+    """Group sizes -> offsets (int32[G + 1]), or None for one group."""
+    if groups is None:
+        return None
+    g = np.asarray(groups)
+    if g.ndim != 1 or len(g) == 0 or not np.issubdtype(g.dtype, np.integer):
+        raise ValueError("groups: a list of group sizes")
+    if int(g.sum()) != n or g.min() < 0:
+        raise ValueError(f"groups: the sizes add to {int(g.sum())}, the lanes number {n}")
+    return np.ascontiguousarray(np.concatenate(([0], np.cumsum(g))), np.int32)
+
+
+def _boot_bufs(n, G, B, per_lane, vmax, boot):
+    return (np.zeros(max(G, 1), BOOT_GROUP_DTYPE), np.zeros(max(n, 1), BOOT_LANE_DTYPE) if per_lane else None,
+            np.zeros(max(G * B, 1), np.int64) if vmax else None, np.zeros(max(n * B, 1), np.int64) if boot else None)
+
+
+def _boot_result(bufs, n, G, B) -> RealityCheck:
+    grp, rec, vm, bt_ = bufs
+    return RealityCheck(grp[:G], B, None if rec is None else rec[:n], None if vm is None else vm[:G * B].reshape(G, B),
+                        None if bt_ is None else bt_[:n * B].reshape(n, B))
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def reality_check_host(equity, n_bars, groups=None, resamples: int = 1000, block: int = 10, seed: int = 0,
+                       window=None, per_lane: bool = False, vmax: bool = False, boot: bool = False) -> RealityCheck:
+    """bt_bootstrap_host: the reality check of n lanes from their replayed equity curves
+    (Replay.equity and Replay.n_bars of Engine.replay(curves=True)) on the CPU (no GPU needed), the
+    scalar restatement of Engine.reality_check: it adds the drawn bars one by one."""
+    eq = np.ascontiguousarray(equity, np.int64)
+    nb = np.ascontiguousarray(np.asarray(n_bars, np.int32))
+    if eq.ndim != 2 or nb.shape != (eq.shape[0],):
+        raise ValueError("equity: an n x stride array, n_bars: n bar counts")
+    n, stride = eq.shape
+    goff = _as_goff(groups, n)
+    G = 1 if goff is None else len(goff) - 1
+    frm, to = (0, 0) if window is None else _window(window)
+    B = int(resamples)
+    bufs = _boot_bufs(n, G, B if 0 < B <= BOOT_MAX_RESAMPLES else 0, per_lane, vmax, boot)
+    _check(sym("bt_bootstrap_host")(n, eq.ctypes.data if eq.size else None, nb.ctypes.data if n else None, stride, G,
+                                    _ptr(goff), frm, to, B, int(block), int(seed) & (2**64 - 1), *(_ptr(b) for b in bufs)))
+    return _boot_result(bufs, n, G, B)
+
+
 def _ratio(num, den) -> np.ndarray:
     """num / den in doubles, 0 where den is 0."""
     num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
@@ -1134,6 +1246,70 @@ class Engine:
         """Device staging budget of trade_stats in bytes: 0 = the default (256 MB). Results are
         identical whatever the budget."""
         _check(sym("bt_set_tstats_budget")(self._h, nbytes))
+
+    # ---- bootstrap reality check (bt_bootstrap / bt_bootstrap_of, k_boot.hip)
+    def reality_check(self, lanes=None, groups=None, resamples: int = 1000, block: int = 10, seed: int = 0,
+                      window=None, per_lane: bool = False, vmax: bool = False, boot: bool = False) -> RealityCheck:
+        """White's bootstrap reality check on the GPU (bt_bootstrap): is the best lane of a group
+        luck? The per-bar pnl increments of all lanes over one window (by default every bar of the
+        longest row) are resampled jointly, `resamples` times in circular blocks of `block` bars,
+        and per group the best centred resampled sum is compared with the observed best sum.
+        `lanes`: what replay takes (at most BOOT_MAX), with `groups` a list of group sizes (None:
+        one group); without lanes every (symbol, param) lane of the resident dataset, one group per
+        symbol. per_lane, vmax and boot ask for the lane records, the V* matrix and the raw
+        resampled sums (boot with lanes only). run() need not have been called."""
+        f = sym("bt_bootstrap")
+        frm, to = (0, 0) if window is None else _window(window)
+        B = int(resamples)
+        Bb = B if 0 < B <= BOOT_MAX_RESAMPLES else 0   # a refused B sizes no buffer
+        if lanes is None:
+            if groups is not None:
+                raise ValueError("reality_check: groups come with lanes; without lanes every symbol is a group")
+            if boot:
+                raise ValueError("reality_check: boot comes with lanes only")
+            S, P = self.stats()["n_symbols"], self.n_params
+            bufs = _boot_bufs(S * P, S, Bb, per_lane, vmax, False)
+            _check(f(self._h, 0, None, 0, None, frm, to, B, int(block), int(seed) & (2**64 - 1), *(_ptr(b) for b in bufs)))
+            return _boot_result(bufs, S * P, S, B)
+        req = as_lanes(lanes)
+        n = len(req)
+        goff = _as_goff(groups, n)
+        G = 1 if goff is None else len(goff) - 1
+        bufs = _boot_bufs(n, G, Bb, per_lane, vmax, boot)
+        keep = req if n else np.zeros(1, LANE_DTYPE)   # lanes != NULL is what selects list mode
+        _check(f(self._h, n, keep.ctypes.data, G, _ptr(goff), frm, to, B, int(block), int(seed) & (2**64 - 1),
+                 *(_ptr(b) for b in bufs)))
+        return _boot_result(bufs, n, G, B)
+
+    def bootstrap_of(self, d, groups=None, resamples: int = 1000, block: int = 10, seed: int = 0,
+                     per_lane: bool = True, vmax: bool = True, boot: bool = False) -> RealityCheck:
+        """The resampling and finish kernels (bt_bootstrap_of) on a caller's increments: an [n, T]
+        integer array with |d| < 2^31, n at most BOOT_MAX. Needs no dataset."""
+        a = np.asarray(d)
+        if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("bootstrap_of: an n x T integer array")
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise ValueError("bootstrap_of: the increments are int32")
+        a = np.ascontiguousarray(a, np.int32)
+        n, T = a.shape
+        goff = _as_goff(groups, n)
+        G = 1 if goff is None else len(goff) - 1
+        B = int(resamples)
+        bufs = _boot_bufs(n, G, B if 0 < B <= BOOT_MAX_RESAMPLES else 0, per_lane, vmax, boot)
+        _check(sym("bt_bootstrap_of")(self._h, n, T, a.ctypes.data if a.size else None, G, _ptr(goff), B, int(block),
+                                      int(seed) & (2**64 - 1), *(_ptr(b) for b in bufs)))
+        return _boot_result(bufs, n, G, B)
+
+    def set_boot_budget(self, nbytes: int) -> None:
+        """Device staging budget of reality_check and bootstrap_of in bytes: 0 = the default
+        (256 MB). Results are identical whatever the budget."""
+        _check(sym("bt_set_boot_budget")(self._h, nbytes))
+
+    def set_boot_row(self, mode: int) -> None:
+        """Where a lane's prefix row lives while it is resampled: 0 = the planner's choice, 1 = LDS
+        (refused at call time when the row does not fit), 2 = device memory. Results are identical
+        either way."""
+        _check(sym("bt_set_boot_row")(self._h, mode))
 
     # ---- portfolio of chosen lanes (bt_portfolio, k_portfolio.hip)
     def portfolio(self, lanes, windows=None, n_bars=None) -> Portfolio:

@@ -487,6 +487,75 @@ int32_t bt_trade_stats_host(int32_t n_trades, const bt_trade* trades, int32_t n_
                             const int64_t* equity, bt_tstats* out);
 int32_t bt_tstats_agg_host(int32_t S, int32_t P, const bt_tstats* recs, bt_tstats_agg* agg);
 int32_t bt_tstats_merge(const bt_tstats_agg* in, int32_t world, int32_t P, bt_tstats_agg* out);
+/* ---- bootstrap reality check (k_boot.hip, bootstrap.cpp; semantics: docs/bootstrap_spec.md).
+ * Is the best lane of a group luck? n lanes in G groups (group g holds lanes goff[g] .. goff[g+1] - 1)
+ * over one window [from_bar, to_bar) of T = to_bar - from_bar bars (to_bar is NOT clipped to a row's
+ * bars, so that T and the resample plan do not depend on the rows a shard holds; from_bar = to_bar
+ * = 0 means [0, B_max), B_max the bars of the longest requested row, in all-lanes mode of the
+ * longest dataset row). Lane i, walked once over its whole series, gives d^i_k = E_(from+k) -
+ * E_(from+k-1) on the window's bars below its bar count and 0 elsewhere. A circular block bootstrap
+ * with blocks of L' = min(L, T) bars (K = ceil(T / L') blocks, the last one truncated so that every
+ * resample draws T bars) resamples all lanes jointly B times: block j of resample b starts at draw
+ * j (0-based) of the SplitMix64 generator of docs/oracle_spec.md §1 keyed by (seed, b), taken
+ * modulo T as an unsigned 64-bit number. S*_(i,b) is lane i's resampled sum, S_i its plain sum.
+ *   lanes_out[i]   bt_boot_lane: sum = S_i, n_nonpos = #{b : S* <= 0}, m1 = sum over b of S*,
+ *                  m2 = sum over b of S*^2 (bt_wide: m1 can pass 2^63);
+ *   groups_out[g]  bt_boot_group: best_sum = max S_i over the group, best_lane the lowest index
+ *                  inside the group that reaches it, n_lanes, and n_ge = #{b : V*_(g,b) >= best_sum}
+ *                  with V*_(g,b) = max over the group of S*_(i,b) - S_i: n_ge / B is White's p-value;
+ *   vmax_out       [G * B] the V*;  boot_out  [n * B] the raw S* (list mode only).
+ * Every figure is an exact integer (|S*| < 2^53); per-group results of shards concatenate.
+ *   list mode (lanes != NULL): n in [1, BT_BOOT_MAX] lanes, repeats allowed; goff == NULL means
+ *     one group (G is then 0 or 1).
+ *   all-lanes mode (lanes == NULL, n == 0, goff == NULL, G == 0): every dataset row's P lanes are
+ *     one group, in dataset order: groups_out[S], lanes_out[S * P], vmax_out[S * B]; boot_out must
+ *     be NULL.
+ * Any output may be NULL, not all. Synchronous like bt_replay; bt_run need not have been called and
+ * nothing another entry point reads changes. Added within ABI 3 (additive). Returns 0, or -1 with
+ * bt_last_error naming the offending value (the engine stays usable): a null engine, no dataset, n
+ * outside its range, goff that does not start at 0, increase strictly or end at n, an unknown
+ * symbol id, param outside [0, P), from_bar < 0, T < 1 or T > 2^22, B outside [1, 65536], L
+ * outside [1, 2^22], all outputs NULL, boot_out in all-lanes mode, a device staging need above
+ * the budget (the bytes are named: the start table K*B*4, vmax G*B*8, the per-lane records, a
+ * requested boot and, when the prefix rows live in device memory, one row). */
+typedef struct bt_boot_lane {         /* 48 bytes */
+    int64_t sum;                                    /* S_i */
+    int64_t n_nonpos;                               /* resamples with S* <= 0 */
+    bt_wide m1, m2;                                 /* sum of S*, sum of S*^2 over the B resamples */
+} bt_boot_lane;
+typedef struct bt_boot_group {        /* 24 bytes */
+    int64_t best_sum;
+    int32_t best_lane, n_lanes;                     /* best_lane counts from the group's first lane */
+    int64_t n_ge;
+} bt_boot_group;
+#define BT_BOOT_MAX (1 << 20)         /* lanes per call in list mode and of bt_bootstrap_of */
+#define BT_BOOT_MAX_RESAMPLES 65536
+int32_t bt_bootstrap(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t G, const int32_t* goff,
+                     int32_t from_bar, int32_t to_bar, int32_t B, int32_t L, uint64_t seed,
+                     bt_boot_group* groups_out,   /* [G] or NULL */
+                     bt_boot_lane* lanes_out,     /* [n] or NULL */
+                     int64_t* vmax_out,           /* [G * B] or NULL */
+                     int64_t* boot_out);          /* [n * B] or NULL */
+/* The same resampling and finish on a caller's increments d[n][T] (row-major int32, |d| < 2^31:
+ * INT32_MIN is refused, with its index named): the way to the ends of the range argument. Works on
+ * any engine (also one without a dataset). n in [1, BT_BOOT_MAX], T in [1, 2^22]. */
+int32_t bt_bootstrap_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t G, const int32_t* goff,
+                        int32_t B, int32_t L, uint64_t seed, bt_boot_group* groups_out, bt_boot_lane* lanes_out,
+                        int64_t* vmax_out, int64_t* boot_out);
+/* Device staging budget of the two calls in bytes: 0 = the default (256 MB). Results are identical
+ * whatever the budget. */
+int32_t bt_set_boot_budget(bt_engine* e, int64_t bytes);
+/* Where a lane's prefix row lives while it is resampled: 0 = the planner's choice, 1 = in LDS
+ * (refused at call time when the row of T + 1 words does not fit), 2 = in device memory. Results
+ * are identical either way. */
+int32_t bt_set_boot_row(bt_engine* e, int32_t mode);
+/* Host, no GPU needed: the scalar restatement from replayed curves (equity rows of `stride` values,
+ * n_bars[i] bars each, as bt_replay returns them), which adds the drawn bars one by one. goff ==
+ * NULL means one group; from_bar = to_bar = 0 means [0, max n_bars). */
+int32_t bt_bootstrap_host(int32_t n, const int64_t* equity, const int32_t* n_bars, int64_t stride, int32_t G,
+                          const int32_t* goff, int32_t from_bar, int32_t to_bar, int32_t B, int32_t L,
+                          uint64_t seed, bt_boot_group* groups_out, bt_boot_lane* lanes_out, int64_t* vmax_out,
+                          int64_t* boot_out);
 /* Average device time of the dominant kernel (BT_FLAG_TIMING), and how many launches. */
 int32_t bt_kernel_timing(bt_engine* e, double* total_ms, int64_t* launches, const char** name);
 int32_t bt_reset_timing(bt_engine* e);

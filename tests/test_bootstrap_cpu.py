@@ -1,0 +1,479 @@
+"""Bootstrap reality check, the parts that need no GPU (docs/bootstrap_spec.md): bt_bootstrap_host
+against the Python-int reference of bootstrap_ref.py on the walked and the staged cases, the
+reference's own shortcuts pinned (the numpy sums to the Python-int ones, the closed forms to the
+general reference), every refusal with its message, the record layouts, the planner (plan_boot
+through tests/plan/boot_plan_driver.cpp), the host code and the planner as stand-alone programs under
+AddressSanitizer and UBSan (tests/asan/boot_driver.cpp), and proof from the references alone that
+the cases of tests/test_gpu_bootstrap.py reach what the kernels can get wrong."""
+import json
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import dbx_amd as D
+from dbx_amd import engine as E
+import bootstrap_ref as R
+import random_cases as RC
+from helpers import assert_staging_layout, build_plan_driver, run_driver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "distributed-backtesting-exploration_amd", "csrc")
+OUTS = dict(per_lane=True, vmax=True, boot=True)
+
+
+def _curves(c, r, sub):
+    """(equity n x stride, n_bars) of a walked sub-case's lanes."""
+    eq = np.zeros((len(sub.lanes), max(c.bars)), np.int64)
+    nb = []
+    for i, (s, p) in enumerate(sub.lanes):
+        e = r.curves[s][p][1]
+        eq[i, :len(e)] = e
+        nb.append(len(e))
+    return eq, nb
+
+
+# ------------------------------------------------------------ (a) the host code to the reference
+@pytest.mark.parametrize("strategy", RC.STRATEGIES)
+def test_host_equals_the_reference_on_the_walked_cases(strategy):
+    for seed in R.WALK_SEEDS:
+        c, r = RC.lane_case(strategy, seed), RC.lane_refs(strategy, seed)
+        for name, sub in R.walk_case(strategy, seed).items():
+            eq, nb = _curves(c, r, sub)
+            got = D.reality_check_host(eq, nb, groups=sub.sizes, resamples=sub.B, block=sub.L, seed=sub.seed,
+                                       window=sub.window, **OUTS)
+            R.assert_same(got, R.walk_ref(strategy, seed, name), f"{strategy} seed {seed} {name}")
+
+
+@pytest.mark.parametrize("T", R.OF_T)
+def test_host_equals_the_reference_on_the_staged_cases(T):
+    """The staged increments as curves: E = the running sum of d, every row T bars long."""
+    for k, c in enumerate(R.of_cases(T)):
+        eq = np.cumsum(c.d.astype(np.int64), axis=1)
+        got = D.reality_check_host(eq, [T] * c.n, groups=c.sizes, resamples=c.B, block=c.L, seed=c.seed, **OUTS)
+        R.assert_same(got, R.of_ref(T, k), f"T {T} L {c.L} B {c.B} n {c.n} groups {c.sizes}")
+
+
+def test_host_equals_the_reference_on_family_a():
+    strategy, grid, series, rows = R.LC._a_case("sma")
+    _, _, want = R.family_a_ref("sma")
+    T = max(len(c) for c, _, _ in series)
+    eq = np.zeros((len(series) * grid.n_params, T), np.int64)
+    nb = []
+    for s, ((c, _, _), (_, trades)) in enumerate(zip(series, rows)):
+        for p in range(grid.n_params):
+            e = R.curves_from_trades(c, trades[p])[1]
+            eq[s * grid.n_params + p, :len(e)] = e
+            nb.append(len(e))
+    got = D.reality_check_host(eq, nb, resamples=R.FAMILY_A.B, block=R.FAMILY_A.L, seed=R.FAMILY_A.seed, **OUTS)
+    R.assert_same(got, want, "family A sma")
+
+
+# ------------------------------------------------------------- (b) the reference's own shortcuts
+def test_numpy_sums_equal_the_python_int_sums():
+    for T, k in ((65, 3), (129, 11), (2, 5)):
+        c = R.of_cases(T)[k]
+        plan = R.bar_plan(T, c.B, c.L, c.seed)
+        d = c.d.tolist()
+        assert R.resampled_sums(d, plan) == R.resampled_sums(d, plan, exact=True)
+    sub = R.walk_case("boll", 1)["inner"]
+    c, r = RC.lane_case("boll", 1), RC.lane_refs("boll", 1)
+    frm, T = R.window_of(c, sub)
+    d = [R.increments(r.curves[s][p][1], c.bars[s], frm, T) for s, p in sub.lanes[:40]]
+    plan = R.bar_plan(T, 16, sub.L, sub.seed)
+    assert R.resampled_sums(d, plan) == R.resampled_sums(d, plan, exact=True)
+    big = [[R.PMAX] * 9, [-R.PMAX, R.PMAX] * 4 + [-R.PMAX]]     # above the numpy path's bound at T = 2^31: forced exact
+    assert R.resampled_sums(big, R.bar_plan(9, 5, 4, 1)) == R.resampled_sums(big, R.bar_plan(9, 5, 4, 1), exact=True)
+
+
+def test_the_draws_are_the_oracle_generator():
+    """draw(seed, b, k) is draw k of docs/oracle_spec.md §1 for symbol b: the first close of the
+    synthetic series of symbol b is 1,000,000 + draw 0 mod 9,000,001."""
+    from replay_ref import gen_hlc
+    for seed, b in ((0x5EED, 0), (0x5EED, 41), (7, 123456)):
+        _, _, c = gen_hlc(seed, b, 2)
+        assert int(c[0]) == 1_000_000 + R.draw(seed, b, 0) % 9_000_001
+
+
+def test_closed_form_of_constant_rows():
+    """S* = c T whatever the plan: pinned to the general reference where that can run, then used
+    at T = 2^22 where it cannot."""
+    for T, L, B in ((64, 7, 9), (65, 64, 5), (129, 200, 3)):
+        c = [R.PMAX, -R.PMAX, 12345]
+        want = R.reality_check([[x] * T for x in c], [0, 2, 3], B, L, 99, exact=True)
+        got = R.constant_ref(c, T, B, sizes=[2, 1])
+        for name in ("groups", "lanes"):
+            assert getattr(got, name).tobytes() == getattr(want, name).tobytes()
+        assert np.array_equal(got.vmax, want.vmax) and np.array_equal(got.boot, want.boot)
+    far = R.constant_ref([R.PMAX, -R.PMAX], 1 << 22, 8)
+    assert 2**53 - 2**23 < int(far.boot[0, 0]) < 2**53 and int(far.boot[1, 0]) == -int(far.boot[0, 0])
+    m1 = R.constant_ref([R.PMAX], 131073, 65536)
+    assert (int(m1.lanes["m1_hi"][0]) << 64 | int(m1.lanes["m1_lo"][0])) == 65536 * R.PMAX * 131073 > 2**63
+
+
+# ----------------------------------------------- (c) the cases reach what the kernels can get wrong
+def _reach(T, B, L, seed):
+    """What the plan of a case contains: wrapping blocks, a block that ends at T exactly, a block
+    that starts at bar 0, a truncated last block, one block only."""
+    lens = R.blocks(T, L)
+    out = set()
+    for row in R.starts(T, B, L, seed):
+        for s, ln in zip(row, lens):
+            if s + ln > T:
+                out.add("wrap")
+            if s + ln == T:
+                out.add("e_is_T")
+            if s == 0:
+                out.add("s_is_0")
+    if T % min(L, T):
+        out.add("truncated")
+    if L >= T:
+        out.add("one_block")
+    return out
+
+
+def _outcomes(ref, B):
+    out = set()
+    if ((ref.groups["n_ge"] > 0) & (ref.groups["n_ge"] < B)).any():
+        out.add("n_ge_inside")
+    if ((ref.lanes["n_nonpos"] > 0) & (ref.lanes["n_nonpos"] < B)).any():
+        out.add("nonpos_inside")
+    return out
+
+
+PLAN_SHAPES_REACHED = {"wrap", "e_is_T", "s_is_0", "truncated", "one_block"}
+
+
+def test_the_staged_cases_reach_every_plan_shape_and_outcome():
+    for T in R.OF_T:
+        got = set()
+        for k, c in enumerate(R.of_cases(T)):
+            got |= _reach(T, c.B, c.L, c.seed) | _outcomes(R.of_ref(T, k), c.B)
+        want = PLAN_SHAPES_REACHED | ({"n_ge_inside", "nonpos_inside"} if T >= 63 else set())
+        if T == 1:
+            want -= {"wrap"}                       # one bar: every block is the whole window
+        if T <= 2:
+            want -= {"truncated"}                  # every legal block length divides 1 and 2
+        assert want <= got, f"T = {T}: missing {want - got}"
+    ns = {c.n for T in R.OF_T for c in R.of_cases(T)}
+    splits = {(len(c.sizes) == 1, len(c.sizes) == c.n, 1 < len(c.sizes) < c.n) for T in R.OF_T for c in R.of_cases(T)}
+    assert ns == set(R.OF_N) and {(False, False, True), (True, False, False), (False, True, False)} <= splits
+    assert any(c.B > 256 and c.B % 64 for T in R.OF_T for c in R.of_cases(T))
+
+
+@pytest.mark.parametrize("strategy", RC.STRATEGIES)
+def test_the_walked_cases_reach_every_plan_shape_and_outcome(strategy):
+    got = set()
+    for seed in R.WALK_SEEDS:
+        c, r = RC.lane_case(strategy, seed), RC.lane_refs(strategy, seed)
+        for name, sub in R.walk_case(strategy, seed).items():
+            frm, T = R.window_of(c, sub)
+            ref = R.walk_ref(strategy, seed, name)
+            got |= _reach(T, sub.B, sub.L, sub.seed) | _outcomes(ref, sub.B)
+            bars = [c.bars[s] for s, _ in sub.lanes]
+            if any(frm < b < frm + T for b in bars):
+                got.add("row_ends_inside")
+            if any(b <= frm for b in bars) and frm > 0:
+                got.add("row_ends_before_from")
+            if frm + T > max(c.bars):
+                got.add("window_past_every_row")
+            if frm > 0 and any(r.curves[s][p][0][frm - 1] != 0 and r.curves[s][p][0][frm] != 0 and c.bars[s] > frm + 1
+                               for s, p in sub.lanes if c.bars[s] > frm):
+                got.add("begins_inside_a_trade")
+            if name == "duplicate":   # the duplicated lane ties for the best sum, and the first of the two is reported
+                sums = ref.lanes["sum"]
+                assert int(sums[-1]) == int(ref.groups["best_sum"][0]) and (sums == sums[-1]).sum() >= 2
+                assert int(ref.groups["best_lane"][0]) == int(np.flatnonzero(sums == sums[-1])[0]) < len(sums) - 1
+                got.add("tie")
+    # the seed test of the GPU file needs V* that are not all zero: at least three of the four seeds have them
+    assert sum(bool(R.walk_ref(strategy, seed, "per_symbol").vmax.any()) for seed in R.WALK_SEEDS) >= 3
+    want = PLAN_SHAPES_REACHED | {"n_ge_inside", "nonpos_inside", "row_ends_inside", "row_ends_before_from",
+                                  "window_past_every_row", "begins_inside_a_trade", "tie"}
+    assert want <= got, f"{strategy}: missing {want - got}"
+
+
+# ----------------------------------------------------------------------------- (d) refusals
+def test_refusals_name_the_value_and_leave_the_library_usable():
+    eq = np.array([[0, 5, -2], [1, 1, 4]], np.int64)
+    nb = np.array([3, 2], np.int32)
+    two, empty = np.array([0, 1, 2], np.int32), np.array([0, 0, 2], np.int32)
+    late, short = np.array([1, 2], np.int32), np.array([0, 1, 1], np.int32)
+    gr = np.zeros(2, D.BOOT_GROUP_DTYPE)
+    host = E.sym("bt_bootstrap_host")
+
+    def last():
+        return D.lib().bt_last_error().decode()
+
+    def still_good():
+        assert host(2, eq.ctypes.data, nb.ctypes.data, 3, 2, two.ctypes.data, 0, 0, 4, 2, 1, gr.ctypes.data, None, None, None) == 0
+        assert gr["best_sum"].tolist() == [-2, 1] and gr["n_lanes"].tolist() == [1, 1]
+
+    q, b, g, o = eq.ctypes.data, nb.ctypes.data, two.ctypes.data, gr.ctypes.data
+    for args, named in (
+        ((0, q, b, 3, 1, None, 0, 0, 4, 2, 1, o), r"bt_bootstrap_host: n = 0 outside \[1, 1048576\]"),
+        ((2, q, b, 3, 2, None, 0, 0, 4, 2, 1, o), r"G = 2 with goff == NULL"),
+        ((2, q, b, 3, 3, g, 0, 0, 4, 2, 1, o), r"G = 3 outside \[1, n = 2\]"),
+        ((2, q, b, 3, 2, empty.ctypes.data, 0, 0, 4, 2, 1, o), r"goff\[1\] = 0 is not above goff\[0\] = 0 \(group 0 is empty\)"),
+        ((2, q, b, 3, 1, late.ctypes.data, 0, 0, 4, 2, 1, o), r"goff\[0\] = 1 is not 0"),
+        ((2, q, b, 3, 2, short.ctypes.data, 0, 0, 4, 2, 1, o), r"goff\[2\] = 1 is not above goff\[1\] = 1"),
+        ((2, q, b, 3, 2, g, -1, 2, 4, 2, 1, o), r"from_bar = -1 is negative"),
+        ((2, q, b, 3, 2, g, 2, 2, 4, 2, 1, o), r"T = 0 bars of the window \[2, 2\) outside \[1, 4194304\]"),
+        ((2, q, b, 3, 2, g, 0, (1 << 22) + 1, 4, 2, 1, o), r"T = 4194305 bars"),
+        ((2, q, b, 3, 2, g, 0, 0, 0, 2, 1, o), r"B = 0 outside \[1, 65536\]"),
+        ((2, q, b, 3, 2, g, 0, 0, 65537, 2, 1, o), r"B = 65537 outside \[1, 65536\]"),
+        ((2, q, b, 3, 2, g, 0, 0, 4, 0, 1, o), r"L = 0 outside \[1, 4194304\]"),
+        ((2, q, b, 3, 2, g, 0, 0, 4, (1 << 22) + 1, 1, o), r"L = 4194305 outside \[1, 4194304\]"),
+        ((2, q, b, 3, 2, g, 0, 0, 4, 2, 1, None), r"groups, lanes, vmax and boot are all NULL"),
+        ((2, None, b, 3, 2, g, 0, 0, 4, 2, 1, o), r"equity and n_bars are required"),
+        ((2, q, b, 2, 2, g, 0, 0, 4, 2, 1, o), r"n_bars = 3 outside \[0, stride = 2\] \(lane 0\)"),
+    ):
+        assert host(*args, None, None, None) == -1
+        assert re.search(named, last()), last()
+        still_good()
+    out = gr.ctypes.data
+    for name, args in (("bt_bootstrap", (None, 0, None, 0, None, 0, 0, 10, 5, 0, out, None, None, None)),
+                       ("bt_bootstrap_of", (None, 1, 1, q, 0, None, 10, 5, 0, out, None, None, None))):
+        assert E.sym(name)(*args) == -1
+        assert re.search(rf"{name}: null engine", last()), last()
+    for name, arg in (("bt_set_boot_budget", 0), ("bt_set_boot_row", 0)):
+        assert E.sym(name)(None, arg) == -1
+        assert re.search(rf"{name}: null engine", last()), last()
+    still_good()
+    with pytest.raises(ValueError, match="the sizes add to 3, the lanes number 2"):
+        D.reality_check_host(eq, nb, groups=[1, 2])
+    with pytest.raises(ValueError, match="n x stride"):
+        D.reality_check_host(eq[0], nb)
+
+
+def test_the_default_window_is_the_longest_row_and_an_explicit_window_is_not_clipped():
+    rng = np.random.default_rng(5)
+    eq = np.cumsum(rng.integers(-40, 50, (3, 30)), axis=1)
+    nb = [30, 12, 1]
+    a = D.reality_check_host(eq, nb, resamples=20, block=4, seed=9, **OUTS)
+    b = D.reality_check_host(eq, nb, resamples=20, block=4, seed=9, window=(0, 30), **OUTS)
+    assert all(getattr(a, f).tobytes() == getattr(b, f).tobytes() for f in ("groups", "lanes", "vmax", "boot"))
+    # T = 45 although no row has more than 30 bars: another plan, the same sums
+    c = D.reality_check_host(eq, nb, resamples=20, block=4, seed=9, window=(0, 45), **OUTS)
+    assert np.array_equal(c.lanes["sum"], a.lanes["sum"]) and not np.array_equal(c.boot, a.boot)
+    d = [R.increments(eq[i], nb[i], 0, 45) for i in range(3)]
+    R.assert_same(c, R.reality_check(d, [0, 3], 20, 4, 9), "window past every row")
+
+
+def test_derived_figures():
+    rec = np.zeros(2, D.BOOT_LANE_DTYPE)
+    star = [[3, -1, 4, 0], [2**62, 2**62, 2**62, 2**62 + 4]]
+    for i, row in enumerate(star):
+        (rec[i]["m1_lo"], rec[i]["m1_hi"]), (rec[i]["m2_lo"], rec[i]["m2_hi"]) = R.wide(sum(row)), R.wide(sum(x * x for x in row))
+        rec[i]["n_nonpos"] = sum(x <= 0 for x in row)
+    grp = np.array([(5, 1, 2, 1)], D.BOOT_GROUP_DTYPE)
+    rc = D.RealityCheck(grp, 4, rec, np.array([[7, -2, 5, 1]], np.int64), None)
+    assert rc.p_value().tolist() == [0.25] and rc.lane_p().tolist() == [0.5, 0.0]
+    # lane 1: m1 past 2^63 and a variance of 3 that doubles would lose
+    assert rc.lane_se().tolist() == [float(np.sqrt(4.25)), float(np.sqrt(3.0))]
+    assert rc.critical(0.75).tolist() == [6] and rc.critical(1.0).tolist() == [8] and rc.critical(0.01).tolist() == [-1]
+    with pytest.raises(ValueError, match="vmax was not asked for"):
+        D.RealityCheck(grp, 4, rec, None, None).critical(0.5)
+    with pytest.raises(ValueError, match="per_lane was not asked for"):
+        D.RealityCheck(grp, 4, None, None, None).lane_se()
+
+
+# ------------------------------------------------------------------------------------ layout
+def test_record_layouts(tmp_path):
+    assert D.BOOT_LANE_DTYPE.itemsize == 48 and D.BOOT_GROUP_DTYPE.itemsize == 24
+    assert D.BOOT_MAX == 1 << 20 and D.BOOT_MAX_RESAMPLES == 65536
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if cc is None:
+        pytest.skip("no C compiler")
+    src = tmp_path / "layout.c"
+    names = {"sum": "sum", "n_nonpos": "n_nonpos", "m1_lo": "m1.lo", "m1_hi": "m1.hi", "m2_lo": "m2.lo", "m2_hi": "m2.hi"}
+    lines = ['    printf("{\\"lane\\": %d, \\"group\\": %d, \\"max\\": %d, \\"maxb\\": %d", (int)sizeof(bt_boot_lane), '
+             '(int)sizeof(bt_boot_group), (int)BT_BOOT_MAX, (int)BT_BOOT_MAX_RESAMPLES);\n']
+    lines += [f'    printf(", \\"lane.{f}\\": %d", (int)offsetof(bt_boot_lane, {c}));\n' for f, c in names.items()]
+    lines += [f'    printf(", \\"group.{f}\\": %d", (int)offsetof(bt_boot_group, {f}));\n' for f in D.BOOT_GROUP_DTYPE.names]
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "bt.h"\nint main(void) {\n' + "".join(lines) +
+                   '    printf("}\\n");\n    return 0;\n}\n')
+    exe = str(tmp_path / "layout")
+    r = subprocess.run([cc, "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                        str(src), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = json.loads(subprocess.run([exe], capture_output=True, text=True, check=True).stdout)
+    assert (got.pop("lane"), got.pop("group"), got.pop("max"), got.pop("maxb")) == (48, 24, 1 << 20, 65536)
+    want = {f"lane.{f}": D.BOOT_LANE_DTYPE.fields[f][1] for f in D.BOOT_LANE_DTYPE.names}
+    want.update({f"group.{f}": D.BOOT_GROUP_DTYPE.fields[f][1] for f in D.BOOT_GROUP_DTYPE.names})
+    assert got == want
+
+
+# ------------------------------------------------------------------------------ (e) planner
+@pytest.fixture(scope="module")
+def plan():
+    exe = build_plan_driver("boot_plan_driver")
+
+    def run(n, G, T, B, L, list_mode=1, staged=0, want_boot=0, cus=256, row=0, budget=0):
+        return run_driver(exe, n, G, T, B, L, int(list_mode), int(staged), int(want_boot), cus, row, budget)
+    return run
+
+
+BUDGET = 256 << 20
+LDS_T = 8127     # the longest window whose row of T + 1 words fits 64 KB of LDS behind 512 bytes of scratch
+
+
+def _up(x):
+    return (x + 255) // 256 * 256
+
+
+def _fixed(n, G, T, B, L, lst, staged, boot):
+    """The bytes held for the whole call, from the text of plan.h."""
+    K = -(-T // min(L, T))
+    return (_up(K * B * 4) + _up((G + 1) * 4) + _up(G * B * 8) + _up(G * 24) + _up(n * 48) + _up(n * B * 8 if boot else 0)
+            + _up(n * 16 if lst else 0) + _up(n * 4 if lst or staged else 0))
+
+
+# name: (n, G, T, B, L, list, staged, boot, row_req, budget_req)
+PLAN_SHAPES = {
+    "config2": (2_000_000, 5000, 2520, 1000, 10, 0, 0, 0, 0, 0),
+    "lds_limit": (400, 1, LDS_T, 1000, 10, 1, 0, 0, 0, 0),
+    "past_lds_limit": (400, 1, LDS_T + 1, 1000, 10, 1, 0, 0, 0, 0),
+    "arena_by_request": (400, 4, 2520, 100, 10, 1, 0, 1, 2, 0),
+    "arena_minute": (64, 1, 491_400, 1000, 100, 1, 0, 0, 0, 0),
+    "one_row_budget": (6, 2, 9000, 50, 33, 1, 0, 0, 0, -1),
+    "three_rows_budget": (7, 7, 9000, 50, 33, 1, 0, 1, 0, -3),
+    "staged_lds": (65, 65, 129, 200, 7, 0, 1, 1, 0, 0),
+    "staged_arena_longest": (2, 1, 1 << 22, 8, 1 << 20, 0, 1, 0, 0, 0),
+    "one_bar": (1, 1, 1, 1, 1, 1, 0, 0, 0, 0),
+}
+
+
+@pytest.mark.parametrize("name", list(PLAN_SHAPES))
+def test_plan_boot_layout_chunks_and_launch_shape(plan, name):
+    n, G, T, B, L, lst, staged, boot, row, req = PLAN_SHAPES[name]
+    fixed = _fixed(n, G, T, B, L, lst, staged, boot)
+    arena = row == 2 or T > LDS_T
+    unit = ((T + 1 + 31) // 32 * 256 if arena else 0) + ((T + 63) // 64 * 256 if staged else 0)
+    if req < 0:        # a budget of exactly -req rows
+        req = fixed + -req * unit
+    pl = plan(n, G, T, B, L, lst, staged, boot, 256, row, req)
+    assert pl == plan(n, G, T, B, L, lst, staged, boot, 256, row, req), "the plan is a function of its arguments"
+    assert (pl["budget"], pl["lds_limit"], pl["red_bytes"], pl["max_waves"]) == (BUDGET, 65536, 512, 4)
+    assert (pl["lane_rec"], pl["group_rec"], pl["lane_ref"]) == (48, 24, 16)
+    lp = min(L, T)
+    assert (pl["T"], pl["Lp"], pl["K"], pl["last_len"]) == (T, lp, -(-T // lp), T - (-(-T // lp) - 1) * lp)
+    assert 1 <= pl["last_len"] <= lp
+    assert pl["row_mode"] == (2 if arena else 1) and pl["row_refused"] == 0
+    assert 1 <= pl["waves"] <= 4 and pl["block"] == 64 * pl["waves"]
+    assert pl["lds_bytes"] == 512 + (0 if arena else (T + 1) * 8) <= 65536
+    assert pl["pitch"] == ((T + 1 + 31) // 32 * 32 if arena else 0) and pl["d_pitch"] == ((T + 63) // 64 * 64 if staged else 0)
+    assert pl["unit_bytes"] == unit and pl["need_bytes"] == max(fixed + unit, 256)
+    budget = req or BUDGET
+    per = pl["per_chunk"]
+    assert 1 <= per <= n and pl["chunks"] == -(-n // per)
+    K = pl["K"]
+    regions = [(pl["o_starts"], K * B * 4), (pl["o_goff"], (G + 1) * 4), (pl["o_vmax"], G * B * 8), (pl["o_groups"], G * 24),
+               (pl["o_rec"], n * 48), (pl["o_boot"], n * B * 8 if boot else 0), (pl["o_lanes"], n * 16 if lst else 0),
+               (pl["o_gid"], n * 4 if lst or staged else 0), (pl["o_rows"], per * pl["pitch"] * 8),
+               (pl["o_d"], per * pl["d_pitch"] * 4)]
+    assert_staging_layout(regions, pl["staging_bytes"], name)
+    assert pl["staging_bytes"] <= budget
+    assert per == n or pl["staging_bytes"] + unit > budget        # as many lanes as fit
+    rows = pl["units"]
+    assert rows[0][0] == 0 and rows[-1][1] == n and all(0 < b - a <= per for a, b in rows)
+    assert pl["starts_block"] == 256 and pl["starts_blocks"] * 256 >= K * B > (pl["starts_blocks"] - 1) * 256
+    assert pl["finish_block"] == 256
+
+
+def test_plan_boot_on_the_shapes_of_the_issue(plan):
+    c2 = plan(2_000_000, 5000, 2520, 1000, 10, 0)
+    assert c2["row_mode"] == 1 and c2["chunks"] == 1 and c2["lds_bytes"] == 512 + 2521 * 8 and c2["K"] == 252
+    assert c2["staging_bytes"] < 160 << 20          # 96 MB of lane records, 40 MB of vmax, 1 MB of starts
+    assert plan(400, 1, LDS_T, 1000, 10)["row_mode"] == 1 and plan(400, 1, LDS_T + 1, 1000, 10)["row_mode"] == 2
+    assert plan(400, 1, LDS_T, 1000, 10)["lds_bytes"] == 65536
+    # mode 1 where the row does not fit: said by the plan, refused by the call
+    assert plan(400, 1, LDS_T + 1, 1000, 10, row=1)["row_refused"] == 1 and plan(400, 1, LDS_T, 1000, 10, row=1)["row_refused"] == 0
+    one = PLAN_SHAPES["one_row_budget"]
+    fixed = _fixed(*one[:8])
+    unit = (9000 + 1 + 31) // 32 * 256
+    assert plan(6, 2, 9000, 50, 33, budget=fixed + unit)["per_chunk"] == 1
+    assert plan(6, 2, 9000, 50, 33, budget=fixed + unit)["chunks"] == 6
+    assert plan(6, 2, 9000, 50, 33, budget=fixed + 2 * unit - 1)["per_chunk"] == 1
+    short = plan(6, 2, 9000, 50, 33, budget=fixed + unit - 1)       # not even one row: refused with the need named
+    assert short["per_chunk"] == 0 and short["chunks"] == 0 and short["staging_bytes"] == 0
+    assert short["need_bytes"] == fixed + unit
+    minute = plan(64, 1, 491_400, 1000, 100)
+    # 64 rows of 3.9 MB and 19.7 MB of starts pass 256 MB together: two chunks
+    assert minute["row_mode"] == 2 and minute["K"] == 4914 and minute["chunks"] == 2
+    assert minute["per_chunk"] == (BUDGET - _fixed(64, 1, 491_400, 1000, 100, 1, 0, 0)) // ((491_401 + 31) // 32 * 256) == 63
+    far = plan(2, 1, 1 << 22, 8, 1 << 20, 0, 1)
+    assert far["row_mode"] == 2 and far["K"] == 4 and far["chunks"] == 1 and far["staging_bytes"] < BUDGET
+
+
+def test_plan_driver_under_asan_and_ubsan():
+    exe = build_plan_driver("boot_plan_driver", sanitize=True)
+    for name in ("three_rows_budget", "staged_arena_longest", "one_bar"):
+        n, G, T, B, L, lst, staged, boot, row, req = PLAN_SHAPES[name]
+        if req < 0:
+            req = _fixed(n, G, T, B, L, lst, staged, boot) + -req * ((T + 1 + 31) // 32 * 256)
+        args = (n, G, T, B, L, lst, staged, boot, 256, row, req)
+        assert run_driver(exe, *args, sanitized=True) == run_driver(build_plan_driver("boot_plan_driver"), *args)
+
+
+# ---------------------------------------------------------------------- (f) under the sanitizers
+RULES = ("null engine", "no dataset loaded", "n = 3 with lanes == NULL (all-lanes mode takes n = 0)",
+         "G = 2 given in all-lanes mode (one group per dataset row: G = 0, goff == NULL)",
+         "boot given in all-lanes mode: it must be NULL", "n = 1048577 outside [1, 1048576]", "d is required", "", "",
+         "T = 0 bars of the window [0, 0) outside [1, 4194304]", "T = -1 bars of the window [5, 4) outside [1, 4194304]", "",
+         "d[1][0] = -2147483648 outside the domain |d| < 2^31",
+         "the call needs 1000 bytes of device staging, above the budget of 999 bytes", "",
+         "a prefix row of T + 1 = 8129 words (65032 bytes) does not fit the LDS row limit of 65024 bytes "
+         "(bt_set_boot_row mode 1)", "")
+REFUSED = ("n = 0 ", "G = 2 with goff == NULL", "G = 3 outside", "group 0 is empty", "goff[0] = 1 is not 0",
+           "goff[2] = 1 is not above", "from_bar = -1", "T = 0 bars", "T = 4194305 bars", "B = 0 ", "B = 65537 ", "L = 0 ",
+           "L = 4194305 ", "all NULL", "equity and n_bars", "n_bars = 3 outside")
+
+
+def test_host_code_under_asan_and_ubsan(tmp_path):
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.skip("g++ missing")
+    exe = str(tmp_path / "boot_asan")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", CSRC,
+                        os.path.join(ROOT, "tests", "asan", "boot_driver.cpp"),
+                        os.path.join(CSRC, "bootstrap.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    # verify_asan_link_order=0: the environment may preload a library ahead of the ASan runtime
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0")
+    for strategy, seed, name in (("sma", 0, "per_symbol"), ("ema_ols", 1, "past_shortest"), ("boll", 2, "beyond"),
+                                 ("boll", 3, "duplicate")):
+        c, rf = RC.lane_case(strategy, seed), RC.lane_refs(strategy, seed)
+        sub = R.walk_case(strategy, seed)[name]
+        want = R.walk_ref(strategy, seed, name)
+        eq, nb = _curves(c, rf, sub)
+        n, G, B = len(sub.lanes), len(sub.sizes), sub.B
+        frm, to = sub.window or (0, 0)
+        has_goff = int(G > 1)
+        fin, fout = str(tmp_path / f"in_{strategy}"), str(tmp_path / f"out_{strategy}")
+        with open(fin, "wb") as f:
+            f.write(np.array([n, G, eq.shape[1], frm, to, B, sub.L, has_goff], np.int32).tobytes())
+            f.write(np.array([sub.seed], np.uint64).tobytes())
+            if has_goff:
+                f.write(np.array(R.goff_of(sub.sizes), np.int32).tobytes())
+            f.write(np.array(nb, np.int32).tobytes() + np.ascontiguousarray(eq, np.int64).tobytes())
+        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=env, timeout=120)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+        raw = open(fout, "rb").read()
+        cuts = np.cumsum([G * 24, n * 48, G * B * 8, n * B * 8])
+        assert len(raw) == cuts[-1]
+        got = D.RealityCheck(np.frombuffer(raw[:cuts[0]], D.BOOT_GROUP_DTYPE), B,
+                             np.frombuffer(raw[cuts[0]:cuts[1]], D.BOOT_LANE_DTYPE),
+                             np.frombuffer(raw[cuts[1]:cuts[2]], np.int64).reshape(G, B),
+                             np.frombuffer(raw[cuts[2]:], np.int64).reshape(n, B))
+        R.assert_same(got, want, f"{strategy} seed {seed} {name}")
+        lines = r.stdout.splitlines()
+        assert lines[-1] == f"ok {n} {G}"
+        refused = [ln for ln in lines if ln.startswith("refused: ")]
+        assert len(refused) == len(REFUSED)
+        for ln, named in zip(refused, REFUSED):
+            assert ln.startswith("refused: bt_bootstrap_host: ") and named in ln, ln
+        assert [ln[len("rule: "):] for ln in lines if ln.startswith("rule: ")] == list(RULES)
