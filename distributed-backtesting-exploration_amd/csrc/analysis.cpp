@@ -1,9 +1,11 @@
-// analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface / bt_surface_of, bt_topk_of,
-// bt_walk_forward, bt_trade_stats, bt_bootstrap / bt_bootstrap_of, bt_portfolio and bt_covariance / bt_gram_of with their settings. Each
-// call checks its arguments with the pure rules of replay.h / surface.h / topk_rules.h / walkfwd.h /
-// tstats.h / bootstrap.h / portfolio.h / covariance.h, asks plan.h for its chunks and its staging layout, realises that layout in the
-// engine's one arena (engine_state.h), launches, and copies the results back before it returns.
-// Nothing is computed on the CPU but the walk-forward totals (walkfwd.cpp).
+// analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface, bt_surface_of, bt_topk_of,
+// bt_walk_forward, bt_trade_stats, bt_bootstrap, bt_bootstrap_of, bt_portfolio, bt_covariance and
+// bt_gram_of, with their settings (bt_set_*). This is the list the other files point to. Each
+// call checks its arguments with the pure rules of its header (replay.h, surface.h, topk_rules.h,
+// walkfwd.h, tstats.h, bootstrap.h, portfolio.h, covariance.h), asks plan.h for its chunks and its
+// staging layout, realises that layout in the engine's one arena (engine_state.h), launches, and
+// copies the results back before it returns. Nothing is computed on the CPU but the walk-forward
+// totals (walkfwd.cpp).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -23,6 +25,9 @@ using namespace bt;
 
 namespace {
 
+// In this file a refusal throws (ABI_GUARD turns it into bt_last_error() and -1): a bare
+// `refuse(fn, why);` ends the call. It hides bt::refuse of host_common.h, which returns -1 and is
+// what the HIP-free files `return`.
 [[noreturn]] void refuse(const char* fn, const std::string& why) { throw HipFail{std::string(fn) + ": " + why}; }
 
 // Every analysis call starts here, after its refusals: every stream drained, then the arena grown
@@ -39,6 +44,26 @@ uint8_t* enter(bt_engine* e, size_t staging_bytes) {
 template <class F>
 void for_chunks(size_t n, size_t per, F fn) {
     for (size_t i0 = 0; i0 < n; i0 += per) fn(i0, std::min(per, n - i0));
+}
+
+// List mode of bt_trade_stats, bt_bootstrap and bt_covariance: the n requests against the dataset,
+// or the refusal. W: the longest requested symbol.
+std::vector<LaneRef> resolve(bt_engine* e, const char* fn, int32_t n, const bt_lane* lanes, int32_t& W) {
+    std::vector<LaneRef> req;
+    const std::string why = lanes_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, req, W);
+    if (!why.empty()) refuse(fn, why);
+    return req;
+}
+
+// A setting of the analysis calls (bt_set_*): v in [0, hi], or v >= 0 with hi < 0, into its field.
+template <class T>
+int32_t set_knob(bt_engine* e, const char* fn, const char* arg, int64_t v, int64_t hi, T EngineState::*field) {
+    if (!e) refuse(fn, "null engine");
+    if (hi < 0 && v < 0) refuse(fn, std::string(arg) + " = " + std::to_string(v) + " is negative");
+    if (hi >= 0 && (v < 0 || v > hi))
+        refuse(fn, std::string(arg) + " = " + std::to_string(v) + " outside [0, " + std::to_string(hi) + "]");
+    e->*field = (T)v;
+    return 0;
 }
 
 // ---- bt_replay: chosen lanes again, with their trades and curves (k_replay.hip)
@@ -263,12 +288,8 @@ int32_t trade_stats_impl(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstat
     const bool list = lanes != nullptr;
     if (list && n == 0) return 0;
     const int32_t S = (int32_t)e->syms.size(), P = e->P;
-    std::vector<LaneRef> req;
-    if (list) {
-        int32_t W = 0;
-        why = lanes_resolve(e->syms.data(), e->syms.size(), P, n, lanes, req, W);
-        if (!why.empty()) refuse(fn, why);
-    }
+    int32_t W = 0;
+    const std::vector<LaneRef> req = list ? resolve(e, fn, n, lanes, W) : std::vector<LaneRef>{};
     const TstatsPlan pl = plan_tstats(list ? n : S, P, list, e->cus, e->tstats_budget);
     if (pl.per_chunk < 1)   // list mode: the record of one lane
         refuse(fn, tstats_budget_refusal(list ? 1 : P, e->tstats_budget > 0 ? e->tstats_budget : (int64_t)kTstatsBudget));
@@ -316,11 +337,13 @@ struct BootOut {
 };
 
 // `req`: the resolved lanes of a list call; `d`: the increments of a staged call; neither: every
-// lane of the dataset, one group per row. `goff`: the groups of a list or staged call (never null
-// there).
+// lane of the dataset, one group per row. `goff`: the groups of a list or staged call, NULL for
+// all their lanes as one group.
 int32_t boot_run(bt_engine* e, const char* fn, int64_t n, int64_t G, const int32_t* goff, const std::vector<LaneRef>* req,
                  const int32_t* d, int32_t from, int32_t T, int32_t B, int32_t L, uint64_t seed, const BootOut& out) {
     const bool list = req != nullptr, staged = d != nullptr;
+    const int32_t one[2] = {0, (int32_t)n};
+    if ((list || staged) && !goff) goff = one, G = 1;
     const BootPlan pl = plan_boot(n, G, T, B, L, list, staged, out.boot != nullptr, e->cus, e->boot_row, e->boot_budget);
     std::string why;
     if (pl.row_refused) why = boot_row_refusal(T, ((size_t)T + 1) * 8, kBootLdsBytes - kBootRedBytes);
@@ -386,14 +409,11 @@ int32_t bootstrap_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t G,
     if (!why.empty()) refuse(fn, why);
     int32_t T = 0;
     if (lanes) {
-        std::vector<LaneRef> req;
         int32_t W = 0;
-        why = lanes_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, req, W);
-        if (!why.empty()) refuse(fn, why);
+        const std::vector<LaneRef> req = resolve(e, fn, n, lanes, W);
         why = boot_window(from_bar, to_bar, W, T);
         if (!why.empty()) refuse(fn, why);
-        const int32_t one[2] = {0, n};
-        return boot_run(e, fn, n, goff ? G : 1, goff ? goff : one, &req, nullptr, from_bar, T, B, L, seed, out);
+        return boot_run(e, fn, n, G, goff, &req, nullptr, from_bar, T, B, L, seed, out);
     }
     why = boot_window(from_bar, to_bar, e->max_bars, T);
     if (!why.empty()) refuse(fn, why);
@@ -411,10 +431,9 @@ int32_t bootstrap_of_impl(bt_engine* e, int32_t n, int32_t T, const int32_t* d, 
     std::string why = e ? boot_window(0, T, 0, Tw) : "";
     if (why.empty()) why = boot_refusal(call);
     if (!why.empty()) refuse(fn, why);
-    why = boot_domain_refusal(n, T, d);
+    why = increments_domain_refusal(n, T, d);
     if (!why.empty()) refuse(fn, why);
-    const int32_t one[2] = {0, n};
-    return boot_run(e, fn, n, goff ? G : 1, goff ? goff : one, nullptr, d, 0, T, B, L, seed, out);
+    return boot_run(e, fn, n, G, goff, nullptr, d, 0, T, B, L, seed, out);
 }
 
 // ---- bt_portfolio: chosen lanes traded together, per bar (k_portfolio.hip)
@@ -493,10 +512,8 @@ int32_t covariance_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t f
     if (!e) refuse(fn, "null engine");
     std::string why = covariance_refusal(!e->syms.empty(), n, lanes != nullptr, from_bar, to_bar, gram || sums || T_out);
     if (!why.empty()) refuse(fn, why);
-    std::vector<LaneRef> req;
-    int32_t W = 0, T = 0;  // W: the longest requested symbol
-    why = lanes_resolve(e->syms.data(), e->syms.size(), e->P, n, lanes, req, W);
-    if (!why.empty()) refuse(fn, why);
+    int32_t W = 0, T = 0;
+    const std::vector<LaneRef> req = resolve(e, fn, n, lanes, W);
     why = covariance_window(from_bar, to_bar, W, T);
     if (!why.empty()) refuse(fn, why);
     const GramPlan pl = plan_gram(n, T, e->cus, e->gram_split);
@@ -532,7 +549,7 @@ int32_t gram_of_impl(bt_engine* e, int32_t n, int32_t T, const int32_t* d, bt_wi
         if (sums) memset(sums, 0, (size_t)n * sizeof(int64_t));
         return 0;
     }
-    why = gram_domain_refusal(n, T, d);
+    why = increments_domain_refusal(n, T, d);
     if (!why.empty()) refuse(fn, why);
     uint8_t* base = enter(e, pl.staging_bytes);
     const GramWork w = gram_work(base, pl, n, T);
@@ -558,12 +575,7 @@ int32_t bt_gram_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, bt_wide
 }
 
 int32_t bt_set_gram_split(bt_engine* e, int32_t k) {
-    ABI_GUARD(-1, {
-        if (!e) refuse("bt_set_gram_split", "null engine");
-        if (k < 0) refuse("bt_set_gram_split", "k = " + std::to_string(k) + " is negative");
-        e->gram_split = k;
-        return 0;
-    })
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_gram_split", "k", k, -1, &EngineState::gram_split); })
 }
 
 int32_t bt_portfolio(bt_engine* e, int32_t n, const bt_pf_lane* lanes, int32_t T, int64_t* pnl, int64_t* equity,
@@ -572,12 +584,7 @@ int32_t bt_portfolio(bt_engine* e, int32_t n, const bt_pf_lane* lanes, int32_t T
 }
 
 int32_t bt_set_portfolio_replicas(bt_engine* e, int32_t r) {
-    ABI_GUARD(-1, {
-        if (!e) refuse("bt_set_portfolio_replicas", "null engine");
-        if (r < 0) refuse("bt_set_portfolio_replicas", "r = " + std::to_string(r) + " is negative");
-        e->portfolio_replicas = r;
-        return 0;
-    })
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_portfolio_replicas", "r", r, -1, &EngineState::portfolio_replicas); })
 }
 
 int32_t bt_replay(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t trade_cap, bt_summary* sum,
@@ -605,12 +612,7 @@ int32_t bt_walk_forward(bt_engine* e, int32_t K, const int32_t* bounds, int32_t 
 }
 
 int32_t bt_set_walkfwd_budget(bt_engine* e, int64_t bytes) {
-    ABI_GUARD(-1, {
-        if (!e) refuse("bt_set_walkfwd_budget", "null engine");
-        if (bytes < 0) refuse("bt_set_walkfwd_budget", "bytes = " + std::to_string(bytes) + " is negative");
-        e->walkfwd_budget = bytes;
-        return 0;
-    })
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_walkfwd_budget", "bytes", bytes, -1, &EngineState::walkfwd_budget); })
 }
 
 int32_t bt_trade_stats(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstats* out, bt_tstats_agg* agg) {
@@ -618,12 +620,7 @@ int32_t bt_trade_stats(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstats*
 }
 
 int32_t bt_set_tstats_budget(bt_engine* e, int64_t bytes) {
-    ABI_GUARD(-1, {
-        if (!e) refuse("bt_set_tstats_budget", "null engine");
-        if (bytes < 0) refuse("bt_set_tstats_budget", "bytes = " + std::to_string(bytes) + " is negative");
-        e->tstats_budget = bytes;
-        return 0;
-    })
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_tstats_budget", "bytes", bytes, -1, &EngineState::tstats_budget); })
 }
 
 int32_t bt_bootstrap(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t G, const int32_t* goff, int32_t from_bar,
@@ -644,30 +641,15 @@ int32_t bt_bootstrap_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, in
 }
 
 int32_t bt_set_boot_budget(bt_engine* e, int64_t bytes) {
-    ABI_GUARD(-1, {
-        if (!e) refuse("bt_set_boot_budget", "null engine");
-        if (bytes < 0) refuse("bt_set_boot_budget", "bytes = " + std::to_string(bytes) + " is negative");
-        e->boot_budget = bytes;
-        return 0;
-    })
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_boot_budget", "bytes", bytes, -1, &EngineState::boot_budget); })
 }
 
 int32_t bt_set_boot_row(bt_engine* e, int32_t mode) {
-    ABI_GUARD(-1, {
-        if (!e) refuse("bt_set_boot_row", "null engine");
-        if (mode < 0 || mode > 2) refuse("bt_set_boot_row", "mode = " + std::to_string(mode) + " outside [0, 2]");
-        e->boot_row = mode;
-        return 0;
-    })
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_boot_row", "mode", mode, 2, &EngineState::boot_row); })
 }
 
 int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks) {
-    ABI_GUARD(-1, {
-        if (!e) refuse("bt_set_surface_chunks", "null engine");
-        if (chunks < 0) refuse("bt_set_surface_chunks", "chunks = " + std::to_string(chunks) + " is negative");
-        e->surface_chunks = chunks;
-        return 0;
-    })
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_surface_chunks", "chunks", chunks, -1, &EngineState::surface_chunks); })
 }
 
 }  // extern "C"

@@ -62,15 +62,6 @@ std::string boot_window(int64_t from_bar, int64_t to_bar, int64_t b_max, int32_t
     return "";
 }
 
-std::string boot_domain_refusal(int64_t n, int64_t T, const int32_t* d) {
-    const int64_t cells = n * T;
-    for (int64_t k = 0; k < cells; ++k)
-        if (d[k] == INT32_MIN)
-            return "d[" + std::to_string(k / T) + "][" + std::to_string(k % T) + "] = " + std::to_string(INT32_MIN) +
-                   " outside the domain |d| < 2^31";
-    return "";
-}
-
 std::string boot_budget_refusal(size_t need_bytes, size_t budget) {
     if (need_bytes <= budget) return "";
     return "the call needs " + std::to_string(need_bytes) + " bytes of device staging, above the budget of " +
@@ -85,18 +76,9 @@ std::string boot_row_refusal(int64_t T, size_t row_bytes, size_t limit_bytes) {
 
 }  // namespace bt
 
-namespace {
-
-typedef __int128 i128;
-
-int32_t refuse(const char* fn, const std::string& why) {
-    bt::set_last_error(std::string(fn) + ": " + why);
-    return -1;
-}
-
-bt_wide wide_of(i128 v) { return bt_wide{(uint64_t)v, (int64_t)(uint64_t)((unsigned __int128)v >> 64)}; }
-
-}  // namespace
+using bt::i128;
+using bt::refuse;
+using bt::wide_rec;
 
 extern "C" {
 
@@ -110,34 +92,15 @@ int32_t bt_bootstrap_host(int32_t n, const int64_t* equity, const int32_t* n_bar
                                 groups_out || lanes_out || vmax_out || boot_out, boot_out != nullptr};
         std::string why = bt::boot_refusal(call);
         if (!why.empty()) return refuse(fn, why);
-        if (!equity || !n_bars) return refuse(fn, "equity and n_bars are required");
-        if (stride < 0) return refuse(fn, "stride = " + std::to_string(stride) + " is negative");
-        int32_t b_max = 0;
-        for (int32_t i = 0; i < n; ++i) {
-            if (n_bars[i] < 0 || n_bars[i] > stride)
-                return refuse(fn, "n_bars = " + std::to_string(n_bars[i]) + " outside [0, stride = " +
-                                      std::to_string(stride) + "] (lane " + std::to_string(i) + ")");
-            b_max = std::max(b_max, n_bars[i]);
-        }
-        int32_t T = 0;
-        why = bt::boot_window(from_bar, to_bar, b_max, T);
+        int32_t b_max = 0, T = 0;
+        why = bt::curves_refusal(n, equity && n_bars, "equity and n_bars", n_bars, stride, "lane", b_max);
+        if (why.empty()) why = bt::boot_window(from_bar, to_bar, b_max, T);
         if (!why.empty()) return refuse(fn, why);
         const int32_t one[2] = {0, n};
         if (!goff) goff = one, G = 1;
 
-        // d[i][k], zero past the lane's own bars
-        std::vector<int64_t> d((size_t)n * (size_t)T, 0);
         std::vector<int64_t> S((size_t)n, 0);
-        for (int32_t i = 0; i < n; ++i) {
-            const int64_t* E = equity + (size_t)i * (size_t)stride;
-            for (int32_t k = 0; k < T; ++k) {
-                const int64_t t = (int64_t)from_bar + k;
-                if (t >= n_bars[i]) break;
-                const int64_t x = E[t] - (t > 0 ? E[t - 1] : 0);
-                d[(size_t)i * (size_t)T + (size_t)k] = x;
-                S[(size_t)i] += x;
-            }
-        }
+        const std::vector<int64_t> d = bt::curve_increments(n, equity, n_bars, stride, from_bar, T, S.data());
         const int32_t Lp = std::min(L, T), K = (T + Lp - 1) / Lp;
         std::vector<i128> m1((size_t)n, 0), m2((size_t)n, 0), star((size_t)n);
         std::vector<int64_t> nonpos((size_t)n, 0), nge((size_t)G, 0), best((size_t)G);
@@ -178,7 +141,7 @@ int32_t bt_bootstrap_host(int32_t n, const int64_t* equity, const int32_t* n_bar
         }
         if (lanes_out)
             for (int32_t i = 0; i < n; ++i)
-                lanes_out[i] = bt_boot_lane{S[(size_t)i], nonpos[(size_t)i], wide_of(m1[(size_t)i]), wide_of(m2[(size_t)i])};
+                lanes_out[i] = bt_boot_lane{S[(size_t)i], nonpos[(size_t)i], wide_rec(m1[(size_t)i]), wide_rec(m2[(size_t)i])};
         if (groups_out)
             for (int32_t g = 0; g < G; ++g)
                 groups_out[g] = bt_boot_group{best[(size_t)g], best_lane[(size_t)g], goff[g + 1] - goff[g], nge[(size_t)g]};

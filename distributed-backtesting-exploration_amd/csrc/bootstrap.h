@@ -7,7 +7,7 @@
 
 #include <string>
 
-#include "../../include/bt.h"
+#include "host_common.h"
 
 static_assert(sizeof(bt_boot_lane) == 48 && offsetof(bt_boot_lane, m1) == 16 && offsetof(bt_boot_lane, m2) == 32,
               "bt_boot_lane layout");
@@ -16,8 +16,6 @@ static_assert(sizeof(bt_boot_group) == 24 && offsetof(bt_boot_group, best_lane) 
               "bt_boot_group layout");
 
 namespace bt {
-
-void set_last_error(const std::string& s);  // bt_last_error() of this thread (engine.cpp)
 
 constexpr int32_t kBootMaxT = 1 << 22;      // bars of a window, and the longest block
 
@@ -45,8 +43,11 @@ std::string boot_groups_refusal(int64_t n, int64_t G, const int32_t* goff);
 // Refuses T < 1 and T > 2^22.
 std::string boot_window(int64_t from_bar, int64_t to_bar, int64_t b_max, int32_t& T);
 
-// d[n][T] of a staged call against |d| < 2^31.
-std::string boot_domain_refusal(int64_t n, int64_t T, const int32_t* d);
+// The old name of increments_domain_refusal (host_common.h), kept like internal.h's ReplayLane:
+// tests/asan/boot_driver.cpp builds with it.
+inline std::string boot_domain_refusal(int64_t n, int64_t T, const int32_t* d) {
+    return increments_domain_refusal(n, T, d);
+}
 
 // The smallest staging the call can run in against the budget.
 std::string boot_budget_refusal(size_t need_bytes, size_t budget);

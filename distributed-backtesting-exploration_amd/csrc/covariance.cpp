@@ -43,15 +43,6 @@ std::string gram_of_refusal(int64_t n, int64_t T, bool have_d, bool any_output) 
     return "";
 }
 
-std::string gram_domain_refusal(int64_t n, int64_t T, const int32_t* d) {
-    const int64_t cells = n * T;
-    for (int64_t k = 0; k < cells; ++k)
-        if (d[k] == INT32_MIN)
-            return "d[" + std::to_string(k / T) + "][" + std::to_string(k % T) + "] = " + std::to_string(INT32_MIN) +
-                   " outside the domain |d| < 2^31";
-    return "";
-}
-
 std::string gram_staging_refusal(size_t staging_bytes, size_t max_bytes, int64_t n, int64_t T) {
     if (staging_bytes <= max_bytes) return "";
     return "n = " + std::to_string(n) + " lanes over T = " + std::to_string(T) + " bars need " +
@@ -60,14 +51,7 @@ std::string gram_staging_refusal(size_t staging_bytes, size_t max_bytes, int64_t
 
 }  // namespace bt
 
-namespace {
-
-int32_t refuse(const char* fn, const std::string& why) {
-    bt::set_last_error(std::string(fn) + ": " + why);
-    return -1;
-}
-
-}  // namespace
+using bt::refuse;
 
 extern "C" {
 
@@ -75,33 +59,12 @@ int32_t bt_covariance_host(int32_t n, const int64_t* equity, const int32_t* n_ba
                            int32_t from_bar, int32_t to_bar, bt_wide* gram, int64_t* sums, int32_t* T_out) {
     const char* fn = "bt_covariance_host";
     try {
-        const std::string why = bt::covariance_refusal(true, n, true, from_bar, to_bar, gram || sums || T_out);
+        std::string why = bt::covariance_refusal(true, n, true, from_bar, to_bar, gram || sums || T_out);
+        int32_t b_max = 0, T = 0;
+        if (why.empty()) why = bt::curves_refusal(n, equity && n_bars, "equity and n_bars", n_bars, stride, "lane", b_max);
+        if (why.empty()) why = bt::covariance_window(from_bar, to_bar, b_max, T);
         if (!why.empty()) return refuse(fn, why);
-        if (n > 0 && (!equity || !n_bars)) return refuse(fn, "equity and n_bars are required");
-        if (n > 0 && stride < 0) return refuse(fn, "stride = " + std::to_string(stride) + " is negative");
-        int32_t b_max = 0;
-        for (int32_t i = 0; i < n; ++i) {
-            if (n_bars[i] < 0 || n_bars[i] > stride)
-                return refuse(fn, "n_bars = " + std::to_string(n_bars[i]) + " outside [0, stride = " +
-                                      std::to_string(stride) + "] (lane " + std::to_string(i) + ")");
-            b_max = std::max(b_max, n_bars[i]);
-        }
-        int32_t T = 0;
-        const std::string w = bt::covariance_window(from_bar, to_bar, b_max, T);
-        if (!w.empty()) return refuse(fn, w);
-        // d[i][t - from_bar], zero past the lane's own bars
-        std::vector<int64_t> d((size_t)n * (size_t)T, 0);
-        for (int32_t i = 0; i < n; ++i) {
-            const int64_t* E = equity + (size_t)i * (size_t)stride;
-            const int32_t end = std::min(from_bar + T, n_bars[i]);
-            int64_t s = 0;
-            for (int32_t t = from_bar; t < end; ++t) {
-                const int64_t x = E[t] - (t > 0 ? E[t - 1] : 0);
-                d[(size_t)i * (size_t)T + (size_t)(t - from_bar)] = x;
-                s += x;
-            }
-            if (sums) sums[i] = s;
-        }
+        const std::vector<int64_t> d = bt::curve_increments(n, equity, n_bars, stride, from_bar, T, sums);
         if (gram)
             for (int32_t i = 0; i < n; ++i)
                 for (int32_t j = i; j < n; ++j) {
@@ -109,7 +72,7 @@ int32_t bt_covariance_host(int32_t n, const int64_t* equity, const int32_t* n_ba
                     const int64_t* b = d.data() + (size_t)j * (size_t)T;
                     __int128 v = 0;
                     for (int32_t t = 0; t < T; ++t) v += (__int128)a[t] * (__int128)b[t];
-                    const bt_wide x{bt::wide_lo(v), bt::wide_hi(v)};
+                    const bt_wide x = bt::wide_rec(v);
                     gram[(size_t)i * (size_t)n + (size_t)j] = x;
                     gram[(size_t)j * (size_t)n + (size_t)i] = x;
                 }

@@ -22,9 +22,11 @@ std::string covariance_window(int32_t from_bar, int32_t to_bar, int32_t b_max, i
 // Why the arguments of bt_gram_of are refused: n, T, the matrix and the outputs.
 std::string gram_of_refusal(int64_t n, int64_t T, bool have_d, bool any_output);
 
-// "" or the refusal of the first element of d[n][T] equal to INT32_MIN, its index named: the
-// domain is |d| < 2^31. Asked once the staging is known to fit.
-std::string gram_domain_refusal(int64_t n, int64_t T, const int32_t* d);
+// The old name of increments_domain_refusal (host_common.h), kept like internal.h's ReplayLane:
+// tests/asan/gram_driver.cpp builds with it.
+inline std::string gram_domain_refusal(int64_t n, int64_t T, const int32_t* d) {
+    return increments_domain_refusal(n, T, d);
+}
 
 // "" or the refusal of a plan whose staging exceeds `max_bytes` (plan.h kGramStagingMax).
 std::string gram_staging_refusal(size_t staging_bytes, size_t max_bytes, int64_t n, int64_t T);

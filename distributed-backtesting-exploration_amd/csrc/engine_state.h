@@ -1,6 +1,6 @@
 // engine_state.h — the engine behind the C ABI's bt_engine handle and the helpers its entry points
-// share: engine.cpp (lifecycle, datasets, runs, batches) and analysis.cpp (replay, surface,
-// walk-forward). Private to the library and not part of the ABI: it includes HIP.
+// share: engine.cpp (lifecycle, datasets, runs, batches) and analysis.cpp (the analysis calls,
+// listed at its head). Private to the library and not part of the ABI: it includes HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -102,12 +102,11 @@ struct EngineState {
     Event ev_batch[4];
     bt_batch_profile prof{};
     int64_t n_errors = 0;
-    // The analysis calls (analysis.cpp: bt_replay, bt_surface, bt_surface_of, bt_walk_forward, bt_trade_stats,
-    // bt_bootstrap, bt_bootstrap_of, bt_portfolio, bt_covariance, bt_gram_of)
-    // share one device staging arena, grown to the staging_bytes of the current call's plan
-    // (plan.h), which lays it out. Sound because every analysis call is synchronous on the engine
-    // stream: it drains every stream on entry and the engine stream before it returns, so no two
-    // of them are in flight together and nothing reads the arena between calls.
+    // The analysis calls (listed at the head of analysis.cpp) share one device staging arena, grown
+    // to the staging_bytes of the current call's plan (plan.h), which lays it out. Sound because
+    // every analysis call is synchronous on the engine stream: it drains every stream on entry and
+    // the engine stream before it returns, so no two of them are in flight together and nothing
+    // reads the arena between calls.
     DevBuf<uint8_t> d_arena;
     int32_t surface_chunks = 0;    // bt_set_surface_chunks (0 = the planner's choice)
     PinnedBuf<uint8_t> h_surface;  // the results of one reduction

@@ -8,9 +8,9 @@
 #include <string>
 #include <utility>
 
-namespace bt {
+#include "host_common.h"
 
-void set_last_error(const std::string& s);  // bt_last_error() of this thread (engine.cpp)
+namespace bt {
 
 struct HipFail { std::string msg; };
 

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/bt.h"
+#include "host_common.h"
 
 // Profiling switches (phase ablation, s_memtime stamps, launch-shape overrides from the
 // environment) exist only in the profiling build (`make PROFILING=1` -> dev/prof.so). In the
@@ -23,8 +24,6 @@
 constexpr int kDbgSlots = 80, kDbgBlocks = 1024;
 
 namespace bt {
-
-typedef __int128 i128;
 
 constexpr int kTile = 64;          // bars per LDS tile (one bit per bar in a 64-bit word)
 constexpr int kRowAlign = 64;      // symbol rows start on 64-element boundaries in HBM
@@ -153,7 +152,10 @@ struct LaneRef {
     int32_t param;
 };
 
-using ReplayLane = LaneRef;        // the name the drivers under tests/plan and tests/asan build with
+// The old name of LaneRef. Three stand-alone drivers (tests/plan/gram_plan_driver.cpp,
+// tests/plan/replay_plan_driver.cpp, tests/asan/gram_driver.cpp) build with it, and 36 test cases
+// build those drivers: it goes when a change may rewrite that many.
+using ReplayLane = LaneRef;
 
 // Replay of chosen lanes (k_replay.hip, bt_replay): one wave64 workgroup per request, which walks
 // the symbol's rows and writes its summary, its first trade_cap trades and, when asked, E_t and
@@ -317,7 +319,6 @@ hipError_t launch_topk(const uint64_t* key, const bt_summary* sum, const SymDesc
 hipError_t launch_topk_init(const TopkWork& w, hipStream_t st);  // once per buffer allocation
 
 // Host-side pieces shared by engine.cpp and comm.cpp.
-void set_last_error(const std::string& s);  // bt_last_error() of this thread
 inline bool topk_less(const bt_topk_rec& a, const bt_topk_rec& b);  // "a ranks before b"
 struct ExchangeView {
     hipStream_t tstream;
@@ -339,14 +340,6 @@ __host__ __device__ inline uint64_t order_key(double x) {
     v.d = x;
     return (v.u >> 63) ? ~v.u : (v.u | 0x8000000000000000ULL);
 }
-
-// An int128 as the (lo, hi) words of the ABI's records, and back.
-__host__ __device__ inline i128 wide_join(uint64_t lo, int64_t hi) {
-    return (i128)(((unsigned __int128)(uint64_t)hi << 64) | lo);
-}
-__host__ __device__ inline uint64_t wide_lo(i128 x) { return (uint64_t)x; }
-__host__ __device__ inline int64_t wide_hi(i128 x) { return (int64_t)(x >> 64); }
-__host__ __device__ inline void wide_split(i128 x, uint64_t& lo, int64_t& hi) { lo = wide_lo(x), hi = wide_hi(x); }
 
 // int128 (lo, hi) -> double, round to nearest, ties to even (spec §4 conversion).
 __host__ __device__ inline double i128_to_double(uint64_t lo, int64_t hi) {

@@ -2,9 +2,9 @@
 // the dataset shape and a CU count (plan.cpp). No HIP call, no device state: the engine
 // (engine.cpp, analysis.cpp) asks for a plan and sizes its buffers from it, the launchers
 // (k_sma.hip, k_ema.hip, k_boll.hip) enqueue what it says, and tests/plan/*_driver.cpp print it without a GPU.
-// The plan of an analysis call (replay, surface, walk-forward) also owns the layout of the call's
-// device staging: the engine allocates staging_bytes, never fewer than 256 for a call it does not
-// refuse, and every region the plan names lies inside them.
+// The plan of an analysis call (listed at the head of analysis.cpp) also owns the layout of the
+// call's device staging: the engine allocates staging_bytes, never fewer than 256 for a call it
+// does not refuse, and every region the plan names lies inside them.
 #pragma once
 #include "internal.h"
 

@@ -98,10 +98,7 @@ void portfolio_finish_host(int32_t T, int32_t n_lanes, int32_t lo, int32_t hi, c
 
 namespace {
 
-int32_t refuse(const char* fn, const std::string& why) {
-    bt::set_last_error(std::string(fn) + ": " + why);
-    return -1;
-}
+using bt::refuse;
 
 // The merged or restated rows into the caller's buffers (any may be NULL).
 void give(int32_t T, const std::vector<int64_t>& pnl, const std::vector<int32_t>& nl, const std::vector<int32_t>& ns,
@@ -126,15 +123,14 @@ int32_t bt_portfolio_host(int32_t n, const int64_t* equity, const int8_t* pos, c
         if (!why.empty()) return refuse(fn, why);
         if (annualization <= 0)
             return refuse(fn, "annualization = " + std::to_string(annualization) + " is not positive");
-        if (n > 0 && (!equity || !pos || !n_bars)) return refuse(fn, "equity, pos and n_bars are required");
-        if (n > 0 && stride < 0) return refuse(fn, "stride = " + std::to_string(stride) + " is negative");
+        int32_t b_max = 0;
+        const std::string c = bt::curves_refusal(n, equity && pos && n_bars, "equity, pos and n_bars", n_bars, stride,
+                                                 "entry", b_max);
+        if (!c.empty()) return refuse(fn, c);
         bt::PfResolved r;
         std::vector<int64_t> pnl((size_t)T, 0);
         std::vector<int32_t> nl((size_t)T, 0), ns((size_t)T, 0);
         for (int32_t i = 0; i < n; ++i) {
-            if (n_bars[i] < 0 || n_bars[i] > stride)
-                return refuse(fn, "n_bars = " + std::to_string(n_bars[i]) + " outside [0, stride = " +
-                                      std::to_string(stride) + "] (entry " + std::to_string(i) + ")");
             int32_t from, to;
             std::string w = bt::portfolio_window(i, lanes[i].from_bar, lanes[i].to_bar, n_bars[i], T, from, to);
             if (!w.empty()) return refuse(fn, w);

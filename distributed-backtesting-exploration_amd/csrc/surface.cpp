@@ -1,7 +1,8 @@
 // surface.cpp — the reductions of a run on the host (docs/surface_spec.md): bt_surface_host, the
 // scalar restatement of what k_surface.hip computes on the device, and bt_surface_merge, the
 // combination of aggregates of disjoint symbol sets (ranks, shards). Written from the spec with
-// the compiler's __int128 and shares no code with the kernels, so that the two check each other.
+// the compiler's __int128 and shares no code with the kernels but the split of an int128 into its
+// words (host_common.h), so that the two check each other.
 // Plain C++: no HIP call, builds with any host compiler.
 #include "surface.h"
 
@@ -26,7 +27,10 @@ std::string surface_refusal(int64_t S, int64_t P, bool have_out, bool bounded, u
 
 namespace {
 
-typedef __int128 i128;
+using bt::i128;
+using bt::refuse;
+using bt::wide_join;
+using bt::wide_split;
 
 // The engine's orderable Sharpe (spec §5): the double's bits, monotone as an unsigned integer.
 uint64_t sharpe_key(double x) {
@@ -48,13 +52,6 @@ bt_param_agg empty_agg() {
     memset(&a, 0, sizeof a);
     a.sym_max = a.sym_min = -1;
     return a;
-}
-
-i128 join(uint64_t lo, int64_t hi) { return (i128)(((unsigned __int128)(uint64_t)hi << 64) | lo); }
-
-void split(i128 v, uint64_t& lo, int64_t& hi) {
-    lo = (uint64_t)v;
-    hi = (int64_t)(uint64_t)((unsigned __int128)v >> 64);
 }
 
 int64_t wrap_add(int64_t a, int64_t b) { return (int64_t)((uint64_t)a + (uint64_t)b); }
@@ -92,10 +89,10 @@ void merge_into(bt_param_agg& a, const bt_param_agg& b) {
         a.sharpe_min = b.sharpe_min;
         a.sym_min = b.sym_min;
     }
-    split((i128)((unsigned __int128)join(a.ss1_lo, a.ss1_hi) + (unsigned __int128)join(b.ss1_lo, b.ss1_hi)),
-          a.ss1_lo, a.ss1_hi);
-    split((i128)((unsigned __int128)join(a.ss2_lo, a.ss2_hi) + (unsigned __int128)join(b.ss2_lo, b.ss2_hi)),
-          a.ss2_lo, a.ss2_hi);
+    wide_split((i128)((unsigned __int128)wide_join(a.ss1_lo, a.ss1_hi) + (unsigned __int128)wide_join(b.ss1_lo, b.ss1_hi)),
+               a.ss1_lo, a.ss1_hi);
+    wide_split((i128)((unsigned __int128)wide_join(a.ss2_lo, a.ss2_hi) + (unsigned __int128)wide_join(b.ss2_lo, b.ss2_hi)),
+               a.ss2_lo, a.ss2_hi);
 }
 
 bt_param_agg column(int32_t S, int32_t P, int32_t p, const bt_summary* sum, const int32_t* ids) {
@@ -131,14 +128,9 @@ bt_param_agg column(int32_t S, int32_t P, int32_t p, const bt_summary* sum, cons
         ss1 += q;
         ss2 += q * q;
     }
-    split(ss1, a.ss1_lo, a.ss1_hi);
-    split(ss2, a.ss2_lo, a.ss2_hi);
+    wide_split(ss1, a.ss1_lo, a.ss1_hi);
+    wide_split(ss2, a.ss2_lo, a.ss2_hi);
     return a;
-}
-
-int32_t refuse(const char* fn, const std::string& why) {
-    bt::set_last_error(std::string(fn) + ": " + why);
-    return -1;
 }
 
 }  // namespace

@@ -5,13 +5,11 @@
 
 #include <string>
 
-#include "../../include/bt.h"
+#include "host_common.h"
 
 static_assert(sizeof(bt_param_agg) == 104, "bt_param_agg layout");
 
 namespace bt {
-
-void set_last_error(const std::string& s);  // bt_last_error() of this thread (engine.cpp)
 
 constexpr int64_t kSurfaceOfMax = 1LL << 22;       // records bt_surface_of stages
 constexpr uint64_t kSurfaceMaxRows = 1ULL << 32;   // dataset rows the int64 sums stay exact below

@@ -1,8 +1,9 @@
 // tstats.cpp — the per-lane trade statistics on the host (docs/tradestats_spec.md): the argument
 // rules of bt_trade_stats, bt_trade_stats_host (one lane's record from its trade list and equity
 // curve), bt_tstats_agg_host (the per-parameter reduction) and bt_tstats_merge. Written from the
-// spec with the compiler's __int128 and shares no code with k_tstats.hip, so that the two check
-// each other. Plain C++: no HIP call, builds with any host compiler.
+// spec with the compiler's __int128 and shares no code with k_tstats.hip but the split of an
+// int128 into its words (host_common.h), so that the two check each other. Plain C++: no HIP call,
+// builds with any host compiler.
 #include "tstats.h"
 
 #include <cstring>
@@ -33,25 +34,16 @@ std::string tstats_budget_refusal(int64_t P, int64_t budget) {
 
 namespace {
 
-typedef __int128 i128;
-
-i128 join(uint64_t lo, int64_t hi) { return (i128)(((unsigned __int128)(uint64_t)hi << 64) | lo); }
-
-void split(i128 v, uint64_t& lo, int64_t& hi) {
-    lo = (uint64_t)v;
-    hi = (int64_t)(uint64_t)((unsigned __int128)v >> 64);
-}
+using bt::i128;
+using bt::refuse;
+using bt::wide_join;
+using bt::wide_split;
 
 // The trade hash of docs/oracle_spec.md §4: one mixed word per trade, summed mod 2^64.
 uint64_t trade_word(int32_t entry_bar, int32_t exit_bar, int32_t side) {
     const uint64_t w = (uint64_t)(uint32_t)entry_bar | (uint64_t)(uint32_t)exit_bar << 31 | (uint64_t)(side > 0) << 62;
     const uint64_t z = (w ^ (w >> 29)) * 0xBF58476D1CE4E5B9ULL;
     return z ^ (z >> 32);
-}
-
-int32_t refuse(const char* fn, const std::string& why) {
-    bt::set_last_error(std::string(fn) + ": " + why);
-    return -1;
 }
 
 template <class T>
@@ -79,7 +71,7 @@ void agg_add(bt_tstats_agg& a, const bt_tstats& r) {
     keep_max(a.max_win, r.max_win);
     keep_max(a.max_loss, r.max_loss);
     keep_max(a.mdd_max, r.mdd);
-    split(join(a.sq_lo, a.sq_hi) + join(r.sq_lo, r.sq_hi), a.sq_lo, a.sq_hi);
+    wide_split(wide_join(a.sq_lo, a.sq_hi) + wide_join(r.sq_lo, r.sq_hi), a.sq_lo, a.sq_hi);
 }
 
 // a += b, two aggregates of disjoint row sets
@@ -102,7 +94,7 @@ void agg_merge(bt_tstats_agg& a, const bt_tstats_agg& b) {
     keep_max(a.max_win, b.max_win);
     keep_max(a.max_loss, b.max_loss);
     keep_max(a.mdd_max, b.mdd_max);
-    split(join(a.sq_lo, a.sq_hi) + join(b.sq_lo, b.sq_hi), a.sq_lo, a.sq_hi);
+    wide_split(wide_join(a.sq_lo, a.sq_hi) + wide_join(b.sq_lo, b.sq_hi), a.sq_lo, a.sq_hi);
 }
 
 }  // namespace
@@ -159,7 +151,7 @@ int32_t bt_trade_stats_host(int32_t n_trades, const bt_trade* trades, int32_t n_
                 win_run = loss_run = 0;
             }
         }
-        split(sq, r.sq_lo, r.sq_hi);
+        wide_split(sq, r.sq_lo, r.sq_hi);
         // the drawdown and the time under water, bar by bar
         int64_t peak = 0;
         int32_t peak_at = 0, run = 0;   // the first bar that holds the running peak (E_0 = 0)

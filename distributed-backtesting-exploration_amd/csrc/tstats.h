@@ -7,7 +7,7 @@
 
 #include <string>
 
-#include "../../include/bt.h"
+#include "host_common.h"
 
 // bt_tstats: four int32 counts, two long counts, two streaks, four hold / bar words (48 bytes),
 // then ten 8-byte words: gross_win, gross_loss, max_win, max_loss, sq (lo, hi), mdd, the two bars,
@@ -25,8 +25,6 @@ static_assert(offsetof(bt_tstats_agg, n_trades) == 24 && offsetof(bt_tstats_agg,
               "bt_tstats_agg layout");
 
 namespace bt {
-
-void set_last_error(const std::string& s);  // bt_last_error() of this thread (engine.cpp)
 
 // Why the arguments of bt_trade_stats are refused ("" = accepted), in the order the call checks
 // them: the dataset, n, the mode (list mode with lanes, all-lanes mode without) and its outputs.

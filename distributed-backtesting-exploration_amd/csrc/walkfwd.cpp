@@ -1,8 +1,9 @@
 // walkfwd.cpp — the walk-forward selection on the host (docs/walkforward_spec.md):
 // bt_walk_forward_host, the scalar restatement of what k_walkfwd.hip's selection computes on the
 // device from the fold records, and the per-row totals, which the device path uses too. Written
-// from the spec with the compiler's __int128 and shares no code with the kernels, so that the two
-// check each other. Plain C++: no HIP call, builds with any host compiler.
+// from the spec with the compiler's __int128 and shares no code with the kernels but the split of
+// an int128 into its words (host_common.h), so that the two check each other. Plain C++: no HIP
+// call, builds with any host compiler.
 #include "walkfwd.h"
 
 #include <cmath>
@@ -38,14 +39,10 @@ std::string walkfwd_refusal(int64_t K, const int32_t* bounds, int64_t train, boo
 
 namespace {
 
-typedef __int128 i128;
-
-i128 join(uint64_t lo, int64_t hi) { return (i128)(((unsigned __int128)(uint64_t)hi << 64) | lo); }
-
-void split(i128 v, uint64_t& lo, int64_t& hi) {
-    lo = (uint64_t)v;
-    hi = (int64_t)(uint64_t)((unsigned __int128)v >> 64);
-}
+using bt::i128;
+using bt::refuse;
+using bt::wide_join;
+using bt::wide_split;
 
 // The engine's orderable Sharpe (spec §5): the double's bits, monotone as an unsigned integer.
 uint64_t sharpe_key(double x) {
@@ -95,8 +92,8 @@ void row_steps(const bt_fold* row, int32_t P, int32_t K, int32_t train, int32_t 
                 i128 s1 = 0, s2 = 0;
                 for (int32_t k = f0; k < j; ++k) {
                     const bt_fold& f = row[(size_t)p * (size_t)K + (size_t)k];
-                    s1 += join(f.s1_lo, f.s1_hi);
-                    s2 += join(f.s2_lo, f.s2_hi);
+                    s1 += wide_join(f.s1_lo, f.s1_hi);
+                    s2 += wide_join(f.s2_lo, f.s2_hi);
                 }
                 const double sh = sharpe_of(s1, s2, n, sqrt_ann);
                 if (s.param < 0 || sharpe_key(sh) > sharpe_key(best)) {  // ties stay with the lower p
@@ -109,11 +106,6 @@ void row_steps(const bt_fold* row, int32_t P, int32_t K, int32_t train, int32_t 
         }
         out[j - j0] = s;
     }
-}
-
-int32_t refuse(const char* fn, const std::string& why) {
-    bt::set_last_error(std::string(fn) + ": " + why);
-    return -1;
 }
 
 }  // namespace
@@ -137,12 +129,12 @@ void walkfwd_totals(int32_t S, int32_t n_steps, const bt_wf_step* steps, double 
             t.pnl += f.pnl;
             t.exposure += f.exposure;
             if (f.mdd > t.mdd) t.mdd = f.mdd;
-            s1 += join(f.s1_lo, f.s1_hi);
-            s2 += join(f.s2_lo, f.s2_hi);
+            s1 += wide_join(f.s1_lo, f.s1_hi);
+            s2 += wide_join(f.s2_lo, f.s2_hi);
             n += n_ret(f);
         }
-        split(s1, t.s1_lo, t.s1_hi);
-        split(s2, t.s2_lo, t.s2_hi);
+        wide_split(s1, t.s1_lo, t.s1_hi);
+        wide_split(s2, t.s2_lo, t.s2_hi);
         t.sharpe = sharpe_of(s1, s2, n, sqrt_ann);
         total[s] = t;
     }

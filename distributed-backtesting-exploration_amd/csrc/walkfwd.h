@@ -5,14 +5,12 @@
 
 #include <string>
 
-#include "../../include/bt.h"
+#include "host_common.h"
 
 static_assert(sizeof(bt_fold) == 80, "bt_fold layout");
 static_assert(sizeof(bt_wf_step) == 104, "bt_wf_step layout");
 
 namespace bt {
-
-void set_last_error(const std::string& s);  // bt_last_error() of this thread (engine.cpp)
 
 constexpr int64_t kWalkfwdFoldsMax = 1LL << 22;    // fold records bt_walk_forward returns
 

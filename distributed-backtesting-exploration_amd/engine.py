@@ -16,6 +16,9 @@ from typing import Sequence
 
 import numpy as np
 
+# the dtypes and constants of include/bt.h: every name of records.py is a name of this module too
+from .records import *  # noqa: F401,F403
+
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # BT_LIB (tuning aid): another in-tree build of the library under dev/, e.g. dev/prof.so (the
 # profiling build, `make PROFILING=1`) or dev/base.so for an A/B; nothing outside the package
@@ -24,93 +27,6 @@ if _bt_lib.startswith("..") or os.path.isabs(_bt_lib):
     raise ImportError(f"BT_LIB={_bt_lib}: a path inside {PKG_DIR} (libbt.so or dev/NAME.so)")
 LIB_PATH = os.path.join(PKG_DIR, _bt_lib)
 CSRC = os.path.join(PKG_DIR, "csrc")
-# include/bt.h BT_ABI_VERSION this wrapper is written against (build() checks the built library)
-ABI_VERSION = 3
-PIPE_SLOTS = 4  # include/bt.h BT_PIPE_SLOTS: pinned read-back / exchange slots
-
-BT_SMA_CROSS, BT_EMA_OLS, BT_BOLL = 1, 2, 3
-BT_FLAG_PARITY, BT_FLAG_TIMING = 1, 2
-BT_DAILY, BT_MINUTE = 0, 1
-
-SUMMARY_DTYPE = np.dtype([
-    ("n_trades", "<i4"), ("status", "<i4"), ("pnl", "<i8"), ("mdd", "<i8"),
-    ("exposure", "<i8"), ("sharpe", "<f8"), ("hash", "<u8"),
-])
-SUMS_DTYPE = np.dtype([("s1_lo", "<u8"), ("s1_hi", "<i8"), ("s2_lo", "<u8"), ("s2_hi", "<i8")])
-TRADE_DTYPE = np.dtype([
-    ("entry_bar", "<i4"), ("exit_bar", "<i4"), ("side", "<i4"), ("pad", "<i4"),
-    ("entry_px", "<i8"), ("exit_px", "<i8"),
-])
-TOPK_DTYPE = np.dtype([("sharpe", "<f8"), ("sym", "<i4"), ("param", "<i4"), ("pnl", "<i8")])
-LANE_DTYPE = np.dtype([("sym", "<i4"), ("param", "<i4")])  # include/bt.h bt_lane
-REPLAY_MAX = 4096  # include/bt.h BT_REPLAY_MAX: lanes per Engine.replay call
-assert SUMMARY_DTYPE.itemsize == 48 and TOPK_DTYPE.itemsize == 24 and TRADE_DTYPE.itemsize == 32
-assert LANE_DTYPE.itemsize == 8
-# include/bt.h bt_param_agg: one parameter's aggregate over every symbol (docs/surface_spec.md)
-PARAM_AGG_DTYPE = np.dtype([
-    ("n_sym", "<i4"), ("n_traded", "<i4"), ("n_win", "<i4"), ("n_pos", "<i4"),
-    ("trades", "<i8"), ("pnl", "<i8"), ("exposure", "<i8"), ("mdd_max", "<i8"),
-    ("sharpe_max", "<f8"), ("sharpe_min", "<f8"), ("sym_max", "<i4"), ("sym_min", "<i4"),
-    ("ss1_lo", "<u8"), ("ss1_hi", "<i8"), ("ss2_lo", "<u8"), ("ss2_hi", "<i8"),
-])
-assert PARAM_AGG_DTYPE.itemsize == 104
-SURFACE_OF_MAX = 1 << 22  # records Engine.surface_of stages (include/bt.h bt_surface_of)
-TOPK_OF_MAX = 1 << 22  # records Engine.topk_of stages (include/bt.h bt_topk_of)
-# include/bt.h bt_fold and bt_wf_step: one lane's result over one bar fold, and one walk-forward
-# step of one symbol (docs/walkforward_spec.md)
-FOLD_DTYPE = np.dtype([
-    ("first_bar", "<i4"), ("n_bars", "<i4"), ("n_trades", "<i4"), ("status", "<i4"),
-    ("pnl", "<i8"), ("mdd", "<i8"), ("exposure", "<i8"), ("sharpe", "<f8"),
-    ("s1_lo", "<u8"), ("s1_hi", "<i8"), ("s2_lo", "<u8"), ("s2_hi", "<i8"),
-])
-WF_STEP_DTYPE = np.dtype([
-    ("sym", "<i4"), ("fold", "<i4"), ("param", "<i4"), ("pad", "<i4"), ("train_sharpe", "<f8"),
-    ("oos", FOLD_DTYPE),
-])
-assert FOLD_DTYPE.itemsize == 80 and WF_STEP_DTYPE.itemsize == 104
-WALKFWD_FOLDS_MAX = 1 << 22  # fold records Engine.walk_forward(folds=True) returns
-# include/bt.h bt_pf_lane and bt_pf_summary: one entry of a portfolio and the summary of its bars
-# (docs/portfolio_spec.md)
-PF_LANE_DTYPE = np.dtype([("sym", "<i4"), ("param", "<i4"), ("from_bar", "<i4"), ("to_bar", "<i4")])
-PF_SUMMARY_DTYPE = np.dtype([
-    ("n_lanes", "<i4"), ("first_bar", "<i4"), ("n_bars", "<i4"), ("max_gross", "<i4"),
-    ("pnl", "<i8"), ("mdd", "<i8"), ("exposure", "<i8"), ("sharpe", "<f8"),
-    ("s1_lo", "<u8"), ("s1_hi", "<i8"), ("s2_lo", "<u8"), ("s2_hi", "<i8"),
-])
-assert PF_LANE_DTYPE.itemsize == 16 and PF_SUMMARY_DTYPE.itemsize == 80
-PORTFOLIO_MAX = 1 << 20  # include/bt.h BT_PORTFOLIO_MAX: entries per Engine.portfolio call
-PF_WHOLE = 2**31 - 1  # to_bar of an entry without a window: every bar of its symbol
-# include/bt.h bt_wide: an int128 as lo/hi words (docs/covariance_spec.md)
-WIDE_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<i8")])
-assert WIDE_DTYPE.itemsize == 16
-COV_MAX = 2048  # include/bt.h BT_COV_MAX: lanes per Engine.covariance call
-# include/bt.h bt_tstats and bt_tstats_agg: one lane's trade statistics and drawdown timing, and one
-# parameter's reduced over every dataset row (docs/tradestats_spec.md)
-TSTATS_DTYPE = np.dtype([
-    ("n_trades", "<i4"), ("n_win", "<i4"), ("n_loss", "<i4"), ("status", "<i4"),
-    ("n_long", "<i4"), ("n_long_win", "<i4"), ("max_win_streak", "<i4"), ("max_loss_streak", "<i4"),
-    ("hold_sum", "<i4"), ("hold_win", "<i4"), ("hold_max", "<i4"), ("n_bars", "<i4"),
-    ("gross_win", "<i8"), ("gross_loss", "<i8"), ("max_win", "<i8"), ("max_loss", "<i8"),
-    ("sq_lo", "<u8"), ("sq_hi", "<i8"), ("mdd", "<i8"), ("mdd_bar", "<i4"), ("peak_bar", "<i4"),
-    ("underwater_bars", "<i4"), ("max_underwater", "<i4"), ("hash", "<u8"),
-])
-TSTATS_AGG_DTYPE = np.dtype([
-    ("n_sym", "<i4"), ("n_traded", "<i4"), ("max_win_streak", "<i4"), ("max_loss_streak", "<i4"),
-    ("hold_max", "<i4"), ("max_underwater", "<i4"),
-    ("n_trades", "<i8"), ("n_win", "<i8"), ("n_loss", "<i8"), ("n_long", "<i8"), ("n_long_win", "<i8"),
-    ("hold_sum", "<i8"), ("hold_win", "<i8"), ("gross_win", "<i8"), ("gross_loss", "<i8"),
-    ("max_win", "<i8"), ("max_loss", "<i8"), ("mdd_max", "<i8"), ("sq_lo", "<u8"), ("sq_hi", "<i8"),
-])
-assert TSTATS_DTYPE.itemsize == 128 and TSTATS_AGG_DTYPE.itemsize == 136
-TSTATS_MAX = 1 << 20  # include/bt.h BT_TSTATS_MAX: lanes per Engine.trade_stats call in list mode
-# include/bt.h bt_boot_lane and bt_boot_group: one lane's and one group's result of the bootstrap
-# reality check (docs/bootstrap_spec.md); m1 and m2 are int128 as lo/hi words
-BOOT_LANE_DTYPE = np.dtype([("sum", "<i8"), ("n_nonpos", "<i8"), ("m1_lo", "<u8"), ("m1_hi", "<i8"),
-                            ("m2_lo", "<u8"), ("m2_hi", "<i8")])
-BOOT_GROUP_DTYPE = np.dtype([("best_sum", "<i8"), ("best_lane", "<i4"), ("n_lanes", "<i4"), ("n_ge", "<i8")])
-assert BOOT_LANE_DTYPE.itemsize == 48 and BOOT_GROUP_DTYPE.itemsize == 24
-BOOT_MAX = 1 << 20  # include/bt.h BT_BOOT_MAX: lanes per call with a lane list, and of bootstrap_of
-BOOT_MAX_RESAMPLES = 65536  # include/bt.h BT_BOOT_MAX_RESAMPLES
 
 
 class BtError(RuntimeError):
@@ -320,6 +236,62 @@ def _arr(v) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(v, dtype=np.int32))
 
 
+def _ptr(a):
+    """An optional array as a pointer argument: NULL for None."""
+    return None if a is None else a.ctypes.data
+
+
+def _list_mode(req) -> np.ndarray:
+    """The lanes argument of a call in which lanes != NULL selects list mode: `req`, or one spare
+    record when there is no request to point at."""
+    return req if len(req) else np.zeros(1, LANE_DTYPE)
+
+
+def _u64(seed) -> int:
+    return int(seed) & (2**64 - 1)
+
+
+def _wide_ints(lo, hi) -> np.ndarray:
+    """int128 values given as arrays of their lo and hi words, as Python ints (an object array)."""
+    vals = [(h << 64) | l for l, h in zip(lo.reshape(-1).tolist(), hi.reshape(-1).tolist())]
+    return np.array(vals, object).reshape(lo.shape)
+
+
+def _wide_f64(lo, hi) -> np.ndarray:
+    """The same values as doubles, each through bt_i128_to_double: one rounding."""
+    vals = [i128_to_double(l, h) for l, h in zip(lo.reshape(-1).tolist(), hi.reshape(-1).tolist())]
+    return np.array(vals, np.float64).reshape(lo.shape)
+
+
+def _as_ids(sym_ids, S) -> np.ndarray:
+    ids = np.ascontiguousarray(np.asarray(sym_ids, np.int32))
+    if ids.shape != (S,):
+        raise ValueError(f"sym_ids: {S} ids for {S} rows, got shape {ids.shape}")
+    return ids
+
+
+def _as_curves(equity, n_bars, *pos):
+    """The curves a *_host call takes (Replay.equity, Replay.n_bars and, where given, Replay.pos
+    of Engine.replay(curves=True)): int64 [n, stride], int32 [n] and int8 [n, stride]."""
+    eq = np.ascontiguousarray(equity, np.int64)
+    ps = [np.ascontiguousarray(p, np.int8) for p in pos]
+    nb = np.ascontiguousarray(np.asarray(n_bars, np.int32))
+    if eq.ndim != 2 or any(p.shape != eq.shape for p in ps) or nb.shape != (eq.shape[0],):
+        raise ValueError("equity and pos: n x stride arrays, n_bars: n bar counts" if pos
+                         else "equity: an n x stride array, n_bars: n bar counts")
+    return (eq, nb, *ps)
+
+
+def _as_increments(d, who) -> np.ndarray:
+    """The [n, T] increments of gram_of and bootstrap_of (`who`, for the message) as int32."""
+    a = np.asarray(d)
+    if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{who}: an n x T integer array")
+    if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+        raise ValueError(f"{who}: the increments are int32")
+    return np.ascontiguousarray(a, np.int32)
+
+
 @dataclass
 class Grid:
     """Worker-side parameter grid (the proto carries none: SURVEY.md §7 hard part 5)."""
@@ -445,8 +417,7 @@ class Surface:
     best: np.ndarray | None       # TOPK_DTYPE[S] (feeds Engine.replay), or None when not asked for
 
     def _sum128(self, name) -> np.ndarray:
-        return np.array([i128_to_double(int(r[name + "_lo"]), int(r[name + "_hi"])) for r in self.params],
-                        np.float64)
+        return _wide_f64(self.params[name + "_lo"], self.params[name + "_hi"])
 
     def mean_sharpe(self) -> np.ndarray:
         """Mean over the symbols of the clamped fixed-point Sharpe (0.0 where n_sym == 0)."""
@@ -489,10 +460,7 @@ def _as_matrix(summaries, sym_ids):
     m = np.ascontiguousarray(summaries, SUMMARY_DTYPE)
     if m.ndim != 2:
         raise ValueError("summaries: an S x P array of SUMMARY_DTYPE")
-    ids = np.ascontiguousarray(np.asarray(sym_ids, np.int32))
-    if ids.shape != (m.shape[0],):
-        raise ValueError(f"sym_ids: {m.shape[0]} ids for {m.shape[0]} rows, got shape {ids.shape}")
-    return m, ids
+    return m, _as_ids(sym_ids, m.shape[0])
 
 
 def surface_host(summaries, sym_ids, best=True) -> Surface:
@@ -501,7 +469,7 @@ def surface_host(summaries, sym_ids, best=True) -> Surface:
     S, P = m.shape
     agg, rec = _surface_bufs(S, P, best)
     _check(sym("bt_surface_host")(S, P, m.ctypes.data if m.size else None, ids.ctypes.data if S else None,
-                                  agg.ctypes.data, None if rec is None else rec.ctypes.data))
+                                  agg.ctypes.data, _ptr(rec)))
     return Surface(agg[:P], None if rec is None else rec[:S])
 
 
@@ -555,9 +523,7 @@ def walk_forward_host(folds, sym_ids, train: int = 1, annualization: int = 252) 
     if f.ndim != 3:
         raise ValueError("folds: an S x P x K array of FOLD_DTYPE")
     S, P, K = f.shape
-    ids = np.ascontiguousarray(np.asarray(sym_ids, np.int32))
-    if ids.shape != (S,):
-        raise ValueError(f"sym_ids: {S} ids for {S} rows, got shape {ids.shape}")
+    ids = _as_ids(sym_ids, S)
     n_steps = max(K - max(train, 1), 0)
     steps = np.zeros((max(S, 1), max(n_steps, 1)), WF_STEP_DTYPE)
     total = np.zeros(max(S, 1), FOLD_DTYPE)
@@ -640,11 +606,7 @@ def portfolio_host(equity, pos, n_bars, windows=None, T=None, annualization: int
     """bt_portfolio_host: the portfolio of n entries from their curves (Replay.equity, Replay.pos
     and Replay.n_bars of Engine.replay(curves=True)) on the CPU (no GPU needed), the scalar
     restatement of Engine.portfolio. `windows` as in as_pf_lanes; T defaults to the longest entry."""
-    eq = np.ascontiguousarray(equity, np.int64)
-    ps = np.ascontiguousarray(pos, np.int8)
-    nb = np.ascontiguousarray(np.asarray(n_bars, np.int32))
-    if eq.ndim != 2 or ps.shape != eq.shape or nb.shape != (eq.shape[0],):
-        raise ValueError("equity and pos: n x stride arrays, n_bars: n bar counts")
+    eq, nb, ps = _as_curves(equity, n_bars, pos)
     n, stride = eq.shape
     req = as_pf_lanes(np.zeros((n, 2), np.int32), windows)
     if T is None:
@@ -687,20 +649,12 @@ class Covariance:
     @property
     def gram(self) -> np.ndarray:
         """[n, n] Python ints."""
-        out = np.empty(self.wide.shape, object)
-        flat = out.reshape(-1)
-        for k, (lo, hi) in enumerate(zip(self.wide["lo"].reshape(-1).tolist(), self.wide["hi"].reshape(-1).tolist())):
-            flat[k] = (hi << 64) | lo
-        return out
+        return _wide_ints(self.wide["lo"], self.wide["hi"])
 
     @property
     def gram_f64(self) -> np.ndarray:
         """[n, n] doubles, every entry through bt_i128_to_double: one rounding."""
-        out = np.empty(self.wide.shape, np.float64)
-        flat = out.reshape(-1)
-        for k, (lo, hi) in enumerate(zip(self.wide["lo"].reshape(-1).tolist(), self.wide["hi"].reshape(-1).tolist())):
-            flat[k] = i128_to_double(lo, hi)
-        return out
+        return _wide_f64(self.wide["lo"], self.wide["hi"])
 
     def cov(self) -> np.ndarray:
         """gram_f64 / T - outer(sums / T, sums / T); zeros when the window has no bar."""
@@ -752,20 +706,13 @@ def covariance_host(equity, n_bars, window=None) -> Covariance:
     """bt_covariance_host: the covariance of n lanes from their replayed equity curves
     (Replay.equity and Replay.n_bars of Engine.replay(curves=True)) on the CPU (no GPU needed), the
     scalar restatement of Engine.covariance."""
-    eq = np.ascontiguousarray(equity, np.int64)
-    nb = np.ascontiguousarray(np.asarray(n_bars, np.int32))
-    if eq.ndim != 2 or nb.shape != (eq.shape[0],):
-        raise ValueError("equity: an n x stride array, n_bars: n bar counts")
+    eq, nb = _as_curves(equity, n_bars)
     n, stride = eq.shape
     frm, to = _window(window)
     wide, sums, T = np.zeros(max(n * n, 1), WIDE_DTYPE), np.zeros(max(n, 1), np.int64), C.c_int32(0)
     _check(sym("bt_covariance_host")(n, eq.ctypes.data if eq.size else None, nb.ctypes.data if n else None, stride,
                                      frm, to, wide.ctypes.data, sums.ctypes.data, C.addressof(T)))
     return _cov_result(n, wide, sums, T.value)
-
-
-def _wide_ints(lo, hi) -> list:
-    return [(h << 64) | l for l, h in zip(lo.reshape(-1).tolist(), hi.reshape(-1).tolist())]
 
 
 @dataclass
@@ -804,7 +751,7 @@ class RealityCheck:
         formed exactly as (B m2 - m1^2) / B^2 in Python ints and then rounded once."""
         r, B = self._lanes(), self.resamples
         m1, m2 = _wide_ints(r["m1_lo"], r["m1_hi"]), _wide_ints(r["m2_lo"], r["m2_hi"])
-        var = [B * b - a * a for a, b in zip(m1, m2)]
+        var = [B * b - a * a for a, b in zip(m1.reshape(-1), m2.reshape(-1))]
         return np.array([float(np.sqrt(v / (B * B))) if v > 0 else 0.0 for v in var], np.float64).reshape(r.shape)
 
     def lane_p(self) -> np.ndarray:
@@ -835,19 +782,12 @@ def _boot_result(bufs, n, G, B) -> RealityCheck:
                         None if bt_ is None else bt_[:n * B].reshape(n, B))
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data
-
-
 def reality_check_host(equity, n_bars, groups=None, resamples: int = 1000, block: int = 10, seed: int = 0,
                        window=None, per_lane: bool = False, vmax: bool = False, boot: bool = False) -> RealityCheck:
     """bt_bootstrap_host: the reality check of n lanes from their replayed equity curves
     (Replay.equity and Replay.n_bars of Engine.replay(curves=True)) on the CPU (no GPU needed), the
     scalar restatement of Engine.reality_check: it adds the drawn bars one by one."""
-    eq = np.ascontiguousarray(equity, np.int64)
-    nb = np.ascontiguousarray(np.asarray(n_bars, np.int32))
-    if eq.ndim != 2 or nb.shape != (eq.shape[0],):
-        raise ValueError("equity: an n x stride array, n_bars: n bar counts")
+    eq, nb = _as_curves(equity, n_bars)
     n, stride = eq.shape
     goff = _as_goff(groups, n)
     G = 1 if goff is None else len(goff) - 1
@@ -855,7 +795,7 @@ def reality_check_host(equity, n_bars, groups=None, resamples: int = 1000, block
     B = int(resamples)
     bufs = _boot_bufs(n, G, B if 0 < B <= BOOT_MAX_RESAMPLES else 0, per_lane, vmax, boot)
     _check(sym("bt_bootstrap_host")(n, eq.ctypes.data if eq.size else None, nb.ctypes.data if n else None, stride, G,
-                                    _ptr(goff), frm, to, B, int(block), int(seed) & (2**64 - 1), *(_ptr(b) for b in bufs)))
+                                    _ptr(goff), frm, to, B, int(block), _u64(seed), *(_ptr(b) for b in bufs)))
     return _boot_result(bufs, n, G, B)
 
 
@@ -881,11 +821,7 @@ class TradeStats:
 
     @staticmethod
     def _sq(r) -> np.ndarray:
-        out = np.empty(r.shape, object)
-        flat = out.reshape(-1)
-        for k, (lo, hi) in enumerate(zip(r["sq_lo"].reshape(-1).tolist(), r["sq_hi"].reshape(-1).tolist())):
-            flat[k] = (hi << 64) | lo
-        return out
+        return _wide_ints(r["sq_lo"], r["sq_hi"])
 
     @property
     def sq(self) -> np.ndarray:
@@ -930,8 +866,7 @@ class TradeStats:
     def trade_std(self, params=False) -> np.ndarray:
         """Population standard deviation of the trade pnl, from sq and the mean."""
         r = self._of(params)
-        sq = np.array([i128_to_double(int(lo), int(hi)) for lo, hi in
-                       zip(r["sq_lo"].reshape(-1).tolist(), r["sq_hi"].reshape(-1).tolist())], np.float64).reshape(r.shape)
+        sq = _wide_f64(r["sq_lo"], r["sq_hi"])
         return np.sqrt(np.maximum(_ratio(sq, r["n_trades"]) - self.expectancy(params) ** 2, 0.0))
 
     def t_stat(self, params=False) -> np.ndarray:
@@ -1032,10 +967,9 @@ class Engine:
         lo = cat(lows) if lows is not None else None
         ids = np.ascontiguousarray(np.arange(len(closes), dtype=np.int64) if sym_ids is None
                                    else np.asarray(sym_ids, np.int64))
-        ptr = lambda a: None if a is None else a.ctypes.data
         self._sym_bars = None
         _check(lib().bt_load_ohlc(self._h, len(closes), ids.ctypes.data, bars.ctypes.data,
-                                  offs.ctypes.data, ptr(h), ptr(lo), c.ctypes.data))
+                                  offs.ctypes.data, _ptr(h), _ptr(lo), c.ctypes.data))
         self.n_symbols = len(closes)
         # the engine keeps ids as int32; with a repeated id the first row wins (bt_replay)
         self._sym_bars = {}
@@ -1112,7 +1046,6 @@ class Engine:
         req = as_lanes(lanes)
         n = len(req)
         f = sym("bt_replay")
-        ptr = lambda a: None if a is None else a.ctypes.data
         summ = np.zeros(max(n, 1), SUMMARY_DTYPE)
         nb = np.zeros(max(n, 1), np.int32)
         tr = np.zeros((max(n, 1), trade_cap), TRADE_DTYPE) if trade_cap > 0 else None
@@ -1123,7 +1056,7 @@ class Engine:
             eq = np.empty((max(n, 1), stride), np.int64)
             ps = np.empty((max(n, 1), stride), np.int8)
         _check(f(self._h, n, req.ctypes.data if n else None, trade_cap, summ.ctypes.data,
-                 nb.ctypes.data, ptr(tr), ptr(eq), ptr(ps), stride))
+                 nb.ctypes.data, _ptr(tr), _ptr(eq), _ptr(ps), stride))
         if curves:
             eq, ps = eq[:n], ps[:n]
             if n == 0:
@@ -1155,7 +1088,7 @@ class Engine:
         f = sym("bt_surface")
         S = self.stats()["n_symbols"]
         agg, rec = _surface_bufs(S, self.n_params, best)
-        _check(f(self._h, agg.ctypes.data, None if rec is None else rec.ctypes.data))
+        _check(f(self._h, agg.ctypes.data, _ptr(rec)))
         return Surface(agg[:self.n_params], None if rec is None else rec[:S])
 
     def surface_of(self, summaries, sym_ids, best: bool = True) -> Surface:
@@ -1165,8 +1098,7 @@ class Engine:
         S, P = m.shape
         agg, rec = _surface_bufs(S, P, best)
         _check(sym("bt_surface_of")(self._h, S, P, m.ctypes.data if m.size else None,
-                                    ids.ctypes.data if S else None, agg.ctypes.data,
-                                    None if rec is None else rec.ctypes.data))
+                                    ids.ctypes.data if S else None, agg.ctypes.data, _ptr(rec)))
         return Surface(agg[:P], None if rec is None else rec[:S])
 
     def topk_of(self, summaries, sym_ids, k: int, lds_free_hist: bool = False) -> np.ndarray:
@@ -1206,8 +1138,7 @@ class Engine:
             if S * self.n_params * max(K, 0) > WALKFWD_FOLDS_MAX:
                 raise BtError(f"bt_walk_forward: S*P*K = {S}*{self.n_params}*{K} exceeds 2^22 fold records")
             rec = np.zeros(max(S * self.n_params * max(K, 0), 1), FOLD_DTYPE)
-        _check(sym("bt_walk_forward")(self._h, K, b.ctypes.data if len(b) else None, train,
-                                      None if rec is None else rec.ctypes.data,
+        _check(sym("bt_walk_forward")(self._h, K, b.ctypes.data if len(b) else None, train, _ptr(rec),
                                       steps.ctypes.data if want else None, total.ctypes.data if want else None))
         return WalkForward(b, train, steps[:S * n_steps].reshape(S, n_steps), total[:S],
                            None if rec is None else rec[:S * self.n_params * K].reshape(S, self.n_params, K))
@@ -1233,13 +1164,13 @@ class Engine:
             req = as_lanes(lanes)
             n = len(req)
             out = np.zeros(max(n, 1), TSTATS_DTYPE)
-            keep = req if n else np.zeros(1, LANE_DTYPE)   # lanes != NULL is what selects list mode
+            keep = _list_mode(req)
             _check(f(self._h, n, keep.ctypes.data, out.ctypes.data, None))
             return TradeStats(out[:n], None)
         S, P = self.stats()["n_symbols"], self.n_params
         out = np.zeros(max(S * P, 1), TSTATS_DTYPE) if per_lane else None
         agg = np.zeros(max(P, 1), TSTATS_AGG_DTYPE) if params else None
-        _check(f(self._h, 0, None, None if out is None else out.ctypes.data, None if agg is None else agg.ctypes.data))
+        _check(f(self._h, 0, None, _ptr(out), _ptr(agg)))
         return TradeStats(None if out is None else out[:S * P].reshape(S, P), None if agg is None else agg[:P])
 
     def set_tstats_budget(self, nbytes: int) -> None:
@@ -1269,15 +1200,15 @@ class Engine:
                 raise ValueError("reality_check: boot comes with lanes only")
             S, P = self.stats()["n_symbols"], self.n_params
             bufs = _boot_bufs(S * P, S, Bb, per_lane, vmax, False)
-            _check(f(self._h, 0, None, 0, None, frm, to, B, int(block), int(seed) & (2**64 - 1), *(_ptr(b) for b in bufs)))
+            _check(f(self._h, 0, None, 0, None, frm, to, B, int(block), _u64(seed), *(_ptr(b) for b in bufs)))
             return _boot_result(bufs, S * P, S, B)
         req = as_lanes(lanes)
         n = len(req)
         goff = _as_goff(groups, n)
         G = 1 if goff is None else len(goff) - 1
         bufs = _boot_bufs(n, G, Bb, per_lane, vmax, boot)
-        keep = req if n else np.zeros(1, LANE_DTYPE)   # lanes != NULL is what selects list mode
-        _check(f(self._h, n, keep.ctypes.data, G, _ptr(goff), frm, to, B, int(block), int(seed) & (2**64 - 1),
+        keep = _list_mode(req)
+        _check(f(self._h, n, keep.ctypes.data, G, _ptr(goff), frm, to, B, int(block), _u64(seed),
                  *(_ptr(b) for b in bufs)))
         return _boot_result(bufs, n, G, B)
 
@@ -1285,19 +1216,14 @@ class Engine:
                      per_lane: bool = True, vmax: bool = True, boot: bool = False) -> RealityCheck:
         """The resampling and finish kernels (bt_bootstrap_of) on a caller's increments: an [n, T]
         integer array with |d| < 2^31, n at most BOOT_MAX. Needs no dataset."""
-        a = np.asarray(d)
-        if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("bootstrap_of: an n x T integer array")
-        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
-            raise ValueError("bootstrap_of: the increments are int32")
-        a = np.ascontiguousarray(a, np.int32)
+        a = _as_increments(d, "bootstrap_of")
         n, T = a.shape
         goff = _as_goff(groups, n)
         G = 1 if goff is None else len(goff) - 1
         B = int(resamples)
         bufs = _boot_bufs(n, G, B if 0 < B <= BOOT_MAX_RESAMPLES else 0, per_lane, vmax, boot)
         _check(sym("bt_bootstrap_of")(self._h, n, T, a.ctypes.data if a.size else None, G, _ptr(goff), B, int(block),
-                                      int(seed) & (2**64 - 1), *(_ptr(b) for b in bufs)))
+                                      _u64(seed), *(_ptr(b) for b in bufs)))
         return _boot_result(bufs, n, G, B)
 
     def set_boot_budget(self, nbytes: int) -> None:
@@ -1367,12 +1293,7 @@ class Engine:
     def gram_of(self, d) -> Covariance:
         """The Gram kernels (bt_gram_of) on a caller's increments: an [n, T] integer array with
         |d| < 2^31, n at most COV_MAX. Needs no dataset."""
-        a = np.asarray(d)
-        if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("gram_of: an n x T integer array")
-        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
-            raise ValueError("gram_of: the increments are int32")
-        a = np.ascontiguousarray(a, np.int32)
+        a = _as_increments(d, "gram_of")
         n, T = a.shape
         wide, sums = np.zeros(max(n * n, 1), WIDE_DTYPE), np.zeros(max(n, 1), np.int64)
         _check(sym("bt_gram_of")(self._h, n, T, a.ctypes.data if a.size else None, wide.ctypes.data,

@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from .engine import BT_DAILY, BT_MINUTE, lib
+from .engine import BT_DAILY, BT_MINUTE, _ptr, lib
 
 MAGIC = b"DBXCOL1\n"
 
@@ -33,7 +33,7 @@ def encode_columns(o, h, lo, c, v=None) -> bytes:
     if vv is not None and len(vv) != n:
         raise ValueError("volume column differs in length")
     L = lib()
-    ptrs = [x.ctypes.data for x in cols] + [None if vv is None else vv.ctypes.data]
+    ptrs = [x.ctypes.data for x in cols] + [_ptr(vv)]
     need = L.bt_encode_columns(*ptrs, n, None, 0)
     if need < 0:
         raise ValueError(L.bt_last_error().decode())

@@ -20,6 +20,62 @@
 #define OFF(T, f) printf("\"%s.%s\": %zu, ", #T, #f, offsetof(T, f))
 #define SZ(T) printf("\"%s\": %zu, ", #T, sizeof(T))
 
+/* Every record the Python mirror keeps as a numpy dtype (records.py RECORDS): its size and the
+ * offset of every field, under the names the mirror uses (OFFN: bt_boot_lane's m1 and m2 lie flat
+ * there). */
+#define OFFN(T, name, f) printf("\"%s.%s\": %zu, ", #T, #name, offsetof(T, f))
+static void records(void) {
+    SZ(bt_summary); OFF(bt_summary, n_trades); OFF(bt_summary, status); OFF(bt_summary, pnl);
+    OFF(bt_summary, mdd); OFF(bt_summary, exposure); OFF(bt_summary, sharpe); OFF(bt_summary, hash);
+    SZ(bt_trade); OFF(bt_trade, entry_bar); OFF(bt_trade, exit_bar); OFF(bt_trade, side);
+    OFF(bt_trade, pad); OFF(bt_trade, entry_px); OFF(bt_trade, exit_px);
+    SZ(bt_sums); OFF(bt_sums, s1_lo); OFF(bt_sums, s1_hi); OFF(bt_sums, s2_lo); OFF(bt_sums, s2_hi);
+    SZ(bt_topk_rec); OFF(bt_topk_rec, sharpe); OFF(bt_topk_rec, sym); OFF(bt_topk_rec, param);
+    OFF(bt_topk_rec, pnl);
+    SZ(bt_lane); OFF(bt_lane, sym); OFF(bt_lane, param);
+    SZ(bt_param_agg); OFF(bt_param_agg, n_sym); OFF(bt_param_agg, n_traded);
+    OFF(bt_param_agg, n_win); OFF(bt_param_agg, n_pos); OFF(bt_param_agg, trades);
+    OFF(bt_param_agg, pnl); OFF(bt_param_agg, exposure); OFF(bt_param_agg, mdd_max);
+    OFF(bt_param_agg, sharpe_max); OFF(bt_param_agg, sharpe_min); OFF(bt_param_agg, sym_max);
+    OFF(bt_param_agg, sym_min); OFF(bt_param_agg, ss1_lo); OFF(bt_param_agg, ss1_hi);
+    OFF(bt_param_agg, ss2_lo); OFF(bt_param_agg, ss2_hi);
+    SZ(bt_fold); OFF(bt_fold, first_bar); OFF(bt_fold, n_bars); OFF(bt_fold, n_trades);
+    OFF(bt_fold, status); OFF(bt_fold, pnl); OFF(bt_fold, mdd); OFF(bt_fold, exposure);
+    OFF(bt_fold, sharpe); OFF(bt_fold, s1_lo); OFF(bt_fold, s1_hi); OFF(bt_fold, s2_lo);
+    OFF(bt_fold, s2_hi);
+    SZ(bt_wf_step); OFF(bt_wf_step, sym); OFF(bt_wf_step, fold); OFF(bt_wf_step, param);
+    OFF(bt_wf_step, pad); OFF(bt_wf_step, train_sharpe); OFF(bt_wf_step, oos);
+    SZ(bt_pf_lane); OFF(bt_pf_lane, sym); OFF(bt_pf_lane, param); OFF(bt_pf_lane, from_bar);
+    OFF(bt_pf_lane, to_bar);
+    SZ(bt_pf_summary); OFF(bt_pf_summary, n_lanes); OFF(bt_pf_summary, first_bar);
+    OFF(bt_pf_summary, n_bars); OFF(bt_pf_summary, max_gross); OFF(bt_pf_summary, pnl);
+    OFF(bt_pf_summary, mdd); OFF(bt_pf_summary, exposure); OFF(bt_pf_summary, sharpe);
+    OFF(bt_pf_summary, s1_lo); OFF(bt_pf_summary, s1_hi); OFF(bt_pf_summary, s2_lo);
+    OFF(bt_pf_summary, s2_hi);
+    SZ(bt_wide); OFF(bt_wide, lo); OFF(bt_wide, hi);
+    SZ(bt_tstats); OFF(bt_tstats, n_trades); OFF(bt_tstats, n_win); OFF(bt_tstats, n_loss);
+    OFF(bt_tstats, status); OFF(bt_tstats, n_long); OFF(bt_tstats, n_long_win);
+    OFF(bt_tstats, max_win_streak); OFF(bt_tstats, max_loss_streak); OFF(bt_tstats, hold_sum);
+    OFF(bt_tstats, hold_win); OFF(bt_tstats, hold_max); OFF(bt_tstats, n_bars);
+    OFF(bt_tstats, gross_win); OFF(bt_tstats, gross_loss); OFF(bt_tstats, max_win);
+    OFF(bt_tstats, max_loss); OFF(bt_tstats, sq_lo); OFF(bt_tstats, sq_hi); OFF(bt_tstats, mdd);
+    OFF(bt_tstats, mdd_bar); OFF(bt_tstats, peak_bar); OFF(bt_tstats, underwater_bars);
+    OFF(bt_tstats, max_underwater); OFF(bt_tstats, hash);
+    SZ(bt_tstats_agg); OFF(bt_tstats_agg, n_sym); OFF(bt_tstats_agg, n_traded);
+    OFF(bt_tstats_agg, max_win_streak); OFF(bt_tstats_agg, max_loss_streak);
+    OFF(bt_tstats_agg, hold_max); OFF(bt_tstats_agg, max_underwater); OFF(bt_tstats_agg, n_trades);
+    OFF(bt_tstats_agg, n_win); OFF(bt_tstats_agg, n_loss); OFF(bt_tstats_agg, n_long);
+    OFF(bt_tstats_agg, n_long_win); OFF(bt_tstats_agg, hold_sum); OFF(bt_tstats_agg, hold_win);
+    OFF(bt_tstats_agg, gross_win); OFF(bt_tstats_agg, gross_loss); OFF(bt_tstats_agg, max_win);
+    OFF(bt_tstats_agg, max_loss); OFF(bt_tstats_agg, mdd_max); OFF(bt_tstats_agg, sq_lo);
+    OFF(bt_tstats_agg, sq_hi);
+    SZ(bt_boot_lane); OFF(bt_boot_lane, sum); OFF(bt_boot_lane, n_nonpos);
+    OFFN(bt_boot_lane, m1_lo, m1.lo); OFFN(bt_boot_lane, m1_hi, m1.hi);
+    OFFN(bt_boot_lane, m2_lo, m2.lo); OFFN(bt_boot_lane, m2_hi, m2.hi);
+    SZ(bt_boot_group); OFF(bt_boot_group, best_sum); OFF(bt_boot_group, best_lane);
+    OFF(bt_boot_group, n_lanes); OFF(bt_boot_group, n_ge);
+}
+
 static int layout(void) {
     printf("{");
     SZ(bt_config);
@@ -31,12 +87,10 @@ static int layout(void) {
     OFF(bt_config, trade_cap); OFF(bt_config, stream);
     SZ(bt_job_in); OFF(bt_job_in, file); OFF(bt_job_in, len);
     SZ(bt_job_out); OFF(bt_job_out, len); OFF(bt_job_out, status); OFF(bt_job_out, n_bars);
-    SZ(bt_summary); OFF(bt_summary, pnl); OFF(bt_summary, sharpe); OFF(bt_summary, hash);
-    SZ(bt_trade); OFF(bt_trade, entry_px);
-    SZ(bt_sums); SZ(bt_topk_rec); OFF(bt_topk_rec, sym); OFF(bt_topk_rec, pnl);
     SZ(bt_stats); SZ(bt_batch_profile); OFF(bt_batch_profile, payload_bytes_read);
     OFF(bt_batch_profile, bars); OFF(bt_batch_profile, host_ingest_ms);
     OFF(bt_batch_profile, total_ms);
+    records();
     printf("\"abi_version\": %d}\n", (int)bt_abi_version());
     return 0;
 }

@@ -185,27 +185,46 @@ def build_abi_host(tmpdir):
     return exe
 
 
+# the structs of bt.h the binding mirrors as ctypes classes; the rest are numpy dtypes (E.RECORDS)
+CTYPES_MIRROR = {"bt_config": E._Config, "bt_job_in": E._JobIn, "bt_job_out": E._JobOut,
+                 "bt_batch_profile": E._BatchProfile, "bt_stats": E._Stats}
+
+
 def test_c99_host_compiles_and_struct_layouts_match_the_python_mirror(tmp_path):
     """bt.h is plain C99 (a Rust / C host binds it as is), and every struct the Python mirror
-    (engine.py ctypes classes and numpy dtypes) reads has the header's size and offsets."""
+    (engine.py ctypes classes, records.py numpy dtypes) reads has the header's size and offsets."""
     exe = build_abi_host(tmp_path)
     got = json.loads(subprocess.run([exe, "layout"], capture_output=True, text=True, check=True).stdout)
     assert got["abi_version"] == 3
-    mirror = {"bt_config": E._Config, "bt_job_in": E._JobIn, "bt_job_out": E._JobOut,
-              "bt_batch_profile": E._BatchProfile, "bt_stats": E._Stats}
-    for cname, cls in mirror.items():
+    for cname, cls in CTYPES_MIRROR.items():
         assert got[cname] == C.sizeof(cls), cname
         for f, _ in cls._fields_:
             key = f"{cname}.{f}"
             if key in got:
                 assert got[key] == getattr(cls, f).offset, key
-    dtypes = {"bt_summary": E.SUMMARY_DTYPE, "bt_trade": E.TRADE_DTYPE, "bt_sums": E.SUMS_DTYPE,
-              "bt_topk_rec": E.TOPK_DTYPE}
-    for cname, dt in dtypes.items():
+    assert len(E.RECORDS) >= 15
+    for k, v in vars(E).items():   # every dtype the binding names is in the table
+        assert not k.endswith("_DTYPE") or any(v is r for r in E.RECORDS.values()), k
+    for cname, dt in E.RECORDS.items():
         assert got[cname] == dt.itemsize, cname
-        for f in dt.names:
-            key = f"{cname}.{f}"
-            if key in got:
-                assert got[key] == dt.fields[f][1], key
+        for f in dt.names:   # every field: one the C host does not print fails here
+            assert got[f"{cname}.{f}"] == dt.fields[f][1], f"{cname}.{f}"
     checked = [k for k in got if "." in k]
     assert len(checked) >= 30
+
+
+def test_every_struct_an_entry_point_takes_is_mirrored():
+    """A struct of bt.h that an entry point the binding calls takes by pointer is a ctypes class
+    or a dtype of RECORDS, so its layout is among those checked above: a record added to the header
+    cannot be forgotten."""
+    hdr = open(os.path.join(ROOT, "include", "bt.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    structs = set(re.findall(r"typedef\s+struct\s+(bt_\w+)\s*\{", hdr))
+    assert len(structs) >= len(CTYPES_MIRROR) + len(E.RECORDS)
+    binding = open(E.__file__).read()
+    protos = re.findall(r"\b(bt_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    called = [(name, args) for name, args in protos if re.search(rf"\b{name}\b", binding)]
+    assert len(called) >= len(E._LATE_SYMBOLS)
+    taken = {t for _, args in called for t in re.findall(r"\b(bt_\w+)\s*\*", args)} & structs
+    assert {"bt_summary", "bt_tstats", "bt_boot_lane", "bt_config", "bt_job_out"} <= taken
+    assert taken <= set(CTYPES_MIRROR) | set(E.RECORDS), sorted(taken - set(CTYPES_MIRROR) - set(E.RECORDS))

@@ -86,6 +86,7 @@ def test_refusals_name_the_value_and_leave_the_library_usable():
         return a
 
     neg, back = lanes_with(17, from_bar=-4), lanes_with(40, from_bar=9, to_bar=8)
+    early = lanes_with(1, from_bar=-4)
     short = nb.copy()
     short[3] = 1001
     e, p, b, l = eq.ctypes.data, ps.ctypes.data, nb.ctypes.data, lanes.ctypes.data
@@ -99,6 +100,8 @@ def test_refusals_name_the_value_and_leave_the_library_usable():
         ((n, e, p, b, 1000, l, 130, 0, *out), r"annualization = 0 is not positive"),
         ((n, None, p, b, 1000, l, 130, 252, *out), r"equity, pos and n_bars are required"),
         ((n, e, p, short.ctypes.data, 1000, l, 130, 252, *out), r"n_bars = 1001 outside \[0, stride = 1000\] \(entry 3\)"),
+        # every n_bars is checked before any window: the later entry's n_bars is what is named
+        ((n, e, p, short.ctypes.data, 1000, early.ctypes.data, 130, 252, *out), r"n_bars = 1001 outside \[0, stride = 1000\] \(entry 3\)"),
         ((n, e, p, b, 1000, neg.ctypes.data, 130, 252, *out), r"from_bar = -4 is negative \(entry 17\)"),
         ((n, e, p, b, 1000, back.ctypes.data, 130, 252, *out), r"to_bar = 8 is below from_bar = 9 \(entry 40\)"),
     ):
