@@ -186,6 +186,82 @@ def of_ref(T, k):
     return reality_check(c.d.tolist(), goff_of(c.sizes), c.B, c.L, c.seed)
 
 
+# ----------------------------------------------- staged cases with groups above 256 lanes
+# boot_finish_kernel has 256 threads: thread t holds lanes t, t + 256, t + 512, .. of its group and
+# keeps the first of equal sums; a tree over the threads then keeps the lower lane. The best row of
+# a group is planted at two lanes (and zeroed where it stood), so that the best sum ties:
+#   "same_thread": lanes 3 and 259, both thread 3's; "two_threads": lanes 5 and 70;
+#   "ends": lane 0 and the group's last.
+FINISH_THREADS = 256
+BIG_T, BIG_B, BIG_L = 65, 64, 7
+# (n, group sizes, the tie planted in each group or None)
+BIG_CASES = (
+    (257, (257,), ("ends",)),                                    # lanes 0 and 256: one thread after all
+    (600, (600,), ("same_thread",)),
+    (600, (300, 1, 299), ("same_thread", None, "two_threads")),
+    (600, (300, 1, 299), ("two_threads", None, "ends")),
+    (577, (256, 321), ("ends", "ends")),                         # a group boundary at lane 256
+)
+
+
+def _tie_lanes(kind, m):
+    return {"same_thread": (3, 3 + FINISH_THREADS), "two_threads": (5, 70), "ends": (0, m - 1)}[kind]
+
+
+@functools.lru_cache(None)
+def big_case(k):
+    """SimpleNamespace(n, sizes, ties [(group, first lane, second lane) within the group], d, seed)
+    of BIG_CASES[k]."""
+    n, sizes, kinds = BIG_CASES[k]
+    rng = np.random.default_rng([0xB16, k])
+    d = rng.integers(-1000, 1100, (n, BIG_T)).astype(np.int32)
+    goff, ties = goff_of(sizes), []
+    for g, kind in enumerate(kinds):
+        if kind is None:
+            continue
+        i0, m = goff[g], sizes[g]
+        best = i0 + int(np.argmax(d[i0:i0 + m].sum(axis=1)))
+        row = d[best].copy()
+        a, b = _tie_lanes(kind, m)
+        assert 0 <= a < b < m
+        d[best] = 0
+        d[i0 + a] = d[i0 + b] = row
+        ties.append((g, a, b))
+    d.setflags(write=False)
+    return SimpleNamespace(n=n, sizes=list(sizes), ties=ties, d=d, seed=0xB16 + k, T=BIG_T, B=BIG_B, L=BIG_L)
+
+
+@functools.lru_cache(None)
+def big_ref(k):
+    c = big_case(k)
+    return reality_check(c.d.tolist(), goff_of(c.sizes), c.B, c.L, c.seed)
+
+
+def _up(x):
+    return (x + 255) // 256 * 256
+
+
+def arena_budget(n, G, T, B, L, lst, boot, per):
+    """The staging budget under which plan_boot takes `per` lanes per chunk on the arena path of a
+    walked call, from the text of plan.h: what is held for the whole call and `per` prefix rows of
+    ceil((T + 1) / 32) lines of 256 bytes."""
+    K = -(-T // min(L, T))
+    fixed = (_up(K * B * 4) + _up((G + 1) * 4) + _up(G * B * 8) + _up(G * 24) + _up(n * 48) + _up(n * B * 8 if boot else 0)
+             + _up(n * 16 if lst else 0) + _up(n * 4 if lst else 0))
+    return fixed + per * ((T + 1 + 31) // 32 * 256)
+
+
+# all-lanes mode in chunks that cut a symbol's group: (strategy, seed, sub-case)
+CUT_CASES = (("sma", 0, "per_symbol"), ("ema_ols", 1, "inner"), ("boll", 2, "past_shortest"))
+
+
+def cut_chunk(S, P):
+    """Lanes per chunk for S rows of P lanes: a third of them, less one where that is a multiple
+    of P, so that chunk boundaries fall inside groups."""
+    per = S * P // 3
+    return per - 1 if per % P == 0 else per
+
+
 PMAX = 2**31 - 1
 
 
@@ -222,6 +298,8 @@ def walk_case(strategy, seed):
     inner_from = 1 if tr is None else (int(tr["entry_bar"]) + int(tr["exit_bar"]) + 1) // 2
     inner_from = max(min(inner_from, longest - 2), 1)
     second = sorted(c.bars)[-2]
+    # the resampling seed: distinct per case for seeds below 16 (WALK_SEEDS are 0 to 3); a wider
+    # sweep of case seeds (BT_RANDOM_SEEDS) reuses resampling seeds across strategies, on other data
     k = RC.STRATEGIES.index(strategy) * 16 + seed
     mk = lambda lanes, sizes, window, L, B=WALK_B: SimpleNamespace(lanes=lanes, sizes=sizes, window=window, B=B, L=L,
                                                                    seed=0x5EED0 + k)
@@ -254,6 +332,55 @@ def walk_ref(strategy, seed, name):
 def sym_lanes(c, sub):
     """The sub-case's lanes as (symbol id, param) pairs."""
     return [(c.ids[s], p) for s, p in sub.lanes]
+
+
+# ------------------------------------------------- window edges of the walked row (ragged rows)
+EDGE_FROM = (0, 1, 63, 64, 65, 127, 128, 129)
+EDGE_LEN = (1, 63, 64, 65, 129)
+EDGE = SimpleNamespace(B=16, L=5, seed=0xED6E)
+
+
+@functools.lru_cache(None)
+def edge_case(strategy):
+    """The ragged rows of tradestats_ref (1, 2, 64, 65, 130 and 700 bars) under the small grid of
+    their strategy: SimpleNamespace(grid, series [(h, l, c)], bars, lanes [(row, param)], sizes (one
+    group per row), curves [equity of lane i, from the oracle's complete trade list])."""
+    import tradestats_ref as TS
+    from replay_ref import oracle_lane
+    grid, series = TS.RAGGED_GRIDS[strategy](), TS.ragged_series(strategy)
+    P = grid.n_params
+    lanes, curves = [], []
+    for s, ohlc in enumerate(series):
+        for p in range(P):
+            summ, tr = oracle_lane(strategy, grid, p, ohlc, cap=len(ohlc[2]))
+            assert int(summ["n_trades"]) == (0 if tr is None else len(tr))
+            lanes.append((s, p))
+            curves.append(curves_from_trades(ohlc[2], tr)[1])
+    return SimpleNamespace(grid=grid, series=series, bars=[len(s[2]) for s in series], lanes=lanes,
+                           sizes=[P] * len(series), curves=curves)
+
+
+@functools.lru_cache(None)
+def edge_ref(strategy, frm, length):
+    c = edge_case(strategy)
+    d = [increments(eq, len(eq), frm, length) for eq in c.curves]
+    return reality_check(d, goff_of(c.sizes), EDGE.B, EDGE.L, EDGE.seed + 1000 * frm + length)
+
+
+# ---------------------------------------------------------- long rows (limit_cases B, C and D)
+def increments_fast(equity, frm, T):
+    """increments for an int64 curve of millions of bars: np.diff over the window's bars, zeros
+    past the row's end."""
+    E = np.asarray(equity, np.int64)
+    t1 = min(frm + T, len(E))
+    out = np.zeros(T, np.int64)
+    if t1 > frm:
+        seg = E[frm - 1:t1] if frm > 0 else np.concatenate([[0], E[:t1]])     # E_(-1) = 0
+        out[:t1 - frm] = np.diff(seg)
+    return out.tolist()
+
+
+LIMITS = SimpleNamespace(B=16, L=100, seed=0x11A17)
 
 
 FAMILY_A = SimpleNamespace(B=32, L=31, seed=0xFA)

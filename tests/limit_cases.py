@@ -223,3 +223,47 @@ def _d_case(name):
     series = [_i32(c, np.minimum(c + rng.integers(0, 3, bars) * (c.max() - c.min()) // 64, PMAX),
                    c - rng.integers(0, 3, bars) * (c.max() - c.min()) // 64) for c in (flat, walk)]
     return strategy, grid, series, _oracle(strategy, grid, series, CAP_D)
+
+
+# ------------------------------------------------ the engines of C and D as the lane tests load them
+def _hlc(series):
+    """This module keeps (c, h, l); the references and the engine loaders take (h, l, c)."""
+    return [(h, lo, c) for c, h, lo in series]
+
+
+# C_GRIDS as they are, and the longest EMA+OLS window on the EMA series: U = sum k c_k passes 2^64
+C_ENGINES = {**{k: (k, v) for k, v in C_GRIDS.items()}, "ema_ols_8512": ("ema_ols", D_GRIDS["ema_ols"][1])}
+
+
+@functools.lru_cache(None)
+def _c_rows(name):
+    """(strategy, grid, (h, l, c), oracle summaries per param) of one engine of family C."""
+    strategy, mk = C_ENGINES[name]
+    grid, series, oracle = _c_case(strategy)
+    hlc = _hlc(series)[0]
+    if name in C_GRIDS:
+        return strategy, grid, hlc, oracle[0][0]
+    grid = mk()
+    return strategy, grid, hlc, oracle_row(strategy, grid, (hlc[2], hlc[0], hlc[1], hlc[2]), grid.annualization)[0]
+
+
+@functools.lru_cache(2)
+def _c_lane(name, p):
+    """(summary, complete trade list) of one lane: up to 460,745 trades, so only two are kept."""
+    from replay_ref import oracle_lane
+    strategy, grid, hlc, rows = _c_rows(name)
+    return oracle_lane(strategy, grid, p, hlc, cap=int(rows[p]["n_trades"]))
+
+
+D_SMA_WIDE = "sma_wide"
+D_ENGINES = list(D_GRIDS) + [D_SMA_WIDE]
+
+
+@functools.lru_cache(None)
+def _d_rows(name):
+    """(strategy, grid, series (c, h, l), oracle rows) of one engine of family D."""
+    if name != D_SMA_WIDE:
+        return _d_case(name)
+    _, _, series, _ = _d_case("sma")
+    grid = D.Grid.sma([8096, 12144], [16192], annualization=98280)
+    return "sma", grid, series, _oracle("sma", grid, series, CAP_D)

@@ -177,6 +177,19 @@ def lane_case(strategy, seed):
     return case
 
 
+LATER_STEPS = ("trade_stats", "reality_check")   # analysis calls that came after STEPS
+
+
+def order_with_later_steps(c):
+    """c.order with LATER_STEPS put in at places drawn by a generator of their own, seeded by the
+    case's strategy and seed: lane_case itself draws what it always drew."""
+    rng = np.random.default_rng([0x0DE1, STRATEGIES.index(c.strategy), c.seed])
+    order = list(c.order)
+    for step in LATER_STEPS:
+        order.insert(int(rng.integers(0, len(order) + 1)), step)
+    return tuple(order)
+
+
 # ------------------------------------------------------------------------------- references
 def summary_matrix(lanes):
     """The oracle's summaries as the S x P matrix Engine.summaries() returns (the engine's record

@@ -195,6 +195,73 @@ def test_the_walked_cases_reach_every_plan_shape_and_outcome(strategy):
     assert want <= got, f"{strategy}: missing {want - got}"
 
 
+def test_the_big_staged_cases_tie_as_planted():
+    """test_gpu_bootstrap.test_staged_groups_above_256_lanes_with_planted_ties: each planted pair
+    is the whole set of lanes that reach the group's best sum, the reference reports the lower one,
+    and the pairs cover one thread of boot_finish_kernel, two threads, and the first and last lane."""
+    kinds, sizes = set(), []
+    for k, (n, _, _) in enumerate(R.BIG_CASES):
+        c, ref = R.big_case(k), R.big_ref(k)
+        goff = R.goff_of(c.sizes)
+        assert 257 <= n == c.n <= 600 and (c.T, c.B) == (65, 64) and c.ties
+        sizes += c.sizes
+        for g, a, b in c.ties:
+            sums = ref.lanes["sum"][goff[g]:goff[g + 1]]
+            best = int(ref.groups["best_sum"][g])
+            assert np.flatnonzero(sums == best).tolist() == [a, b] and best == int(sums.max()) > 0
+            assert int(ref.groups["best_lane"][g]) == a < b
+            if a % R.FINISH_THREADS == b % R.FINISH_THREADS:
+                kinds.add("one_thread")           # decided by the thread's own loop: b = a + 256 k
+            else:
+                kinds.add("two_threads")          # decided by the tree
+            if (a, b) == (0, c.sizes[g] - 1):
+                kinds.add("first_and_last")
+        # the host restatement agrees
+        got = D.reality_check_host(np.cumsum(c.d.astype(np.int64), axis=1), [c.T] * c.n, groups=c.sizes,
+                                   resamples=c.B, block=c.L, seed=c.seed, **OUTS)
+        R.assert_same(got, ref, f"big case {k}")
+    assert kinds == {"one_thread", "two_threads", "first_and_last"}
+    assert max(sizes) == 600 > 2 * R.FINISH_THREADS and 1 in sizes and 256 in sizes
+    assert any(R.goff_of(R.big_case(k).sizes)[1] == 256 for k in range(len(R.BIG_CASES)))   # a boundary at lane 256
+    assert {tuple(R.big_case(k).sizes) for k in range(len(R.BIG_CASES))} >= {(600,), (300, 1, 299)}
+
+
+def test_the_window_edge_cases_reach_the_edges():
+    """test_gpu_bootstrap.test_window_edges_on_ragged_rows, from the lengths and the curves alone."""
+    assert R.EDGE_FROM == (0, 1, 63, 64, 65, 127, 128, 129) and R.EDGE_LEN == (1, 63, 64, 65, 129) and R.EDGE.B == 16
+    for strategy in RC.STRATEGIES:
+        c = R.edge_case(strategy)
+        assert c.bars == [1, 2, 64, 65, 130, 700] and len(c.lanes) == 6 * c.grid.n_params
+        got = set()
+        for frm in R.EDGE_FROM:
+            for length in R.EDGE_LEN:
+                for b in c.bars:
+                    got.add("ends_at_from" if b == frm else "ends_at_from_plus_1" if b == frm + 1 else
+                            "ends_inside" if frm + 1 < b < frm + length else "ends_at_to" if b == frm + length else "other")
+                if (frm + length) % 64 == 0:
+                    got.add("window_ends_on_a_tile_edge")
+        assert got >= {"ends_at_from", "ends_at_from_plus_1", "ends_inside", "ends_at_to", "window_ends_on_a_tile_edge"}
+        # E_(from - 1) is not zero where it is the last bar of the tile before the window's first
+        # (from = 64, 128) and where it is the tile's first bar (65, 129): a base taken from the
+        # wrong tile, or not taken, shows
+        for frm in (63, 64, 65, 127, 128, 129):
+            assert sum(len(eq) > frm and int(eq[frm - 1]) != 0 for eq in c.curves) >= 3, (strategy, frm)
+        # the references move: most windows have lanes with non-zero sums, and the host code agrees
+        moving = 0
+        for frm in R.EDGE_FROM:
+            for length in R.EDGE_LEN:
+                ref = R.edge_ref(strategy, frm, length)
+                moving += bool(ref.lanes["sum"].any())
+                eq = np.zeros((len(c.curves), 700), np.int64)
+                for i, x in enumerate(c.curves):
+                    eq[i, :len(x)] = x
+                host = D.reality_check_host(eq, [len(x) for x in c.curves], groups=c.sizes, resamples=R.EDGE.B,
+                                            block=R.EDGE.L, seed=R.EDGE.seed + 1000 * frm + length,
+                                            window=(frm, frm + length), **OUTS)
+                R.assert_same(host, ref, f"{strategy} window [{frm}, {frm + length})")
+        assert moving >= 30, (strategy, moving)
+
+
 # ----------------------------------------------------------------------------- (d) refusals
 def test_refusals_name_the_value_and_leave_the_library_usable():
     eq = np.array([[0, 5, -2], [1, 1, 4]], np.int64)
@@ -406,6 +473,25 @@ def test_plan_boot_on_the_shapes_of_the_issue(plan):
     assert minute["per_chunk"] == (BUDGET - _fixed(64, 1, 491_400, 1000, 100, 1, 0, 0)) // ((491_401 + 31) // 32 * 256) == 63
     far = plan(2, 1, 1 << 22, 8, 1 << 20, 0, 1)
     assert far["row_mode"] == 2 and far["K"] == 4 and far["chunks"] == 1 and far["staging_bytes"] < BUDGET
+
+
+def test_the_cut_cases_cut_groups_in_three_or_more_chunks(plan):
+    """test_gpu_bootstrap.test_all_lanes_mode_in_chunks_that_cut_a_group: under the budget the test
+    sets, the planner takes the arena rows in at least three chunks whose size is no multiple of P,
+    and a chunk boundary falls inside a row's group."""
+    for strategy, seed, name in R.CUT_CASES:
+        c = RC.lane_case(strategy, seed)
+        sub = R.walk_case(strategy, seed)[name]
+        S, P = len(c.series), c.grid.n_params
+        _, T = R.window_of(c, sub)
+        per = R.cut_chunk(S, P)
+        budget = R.arena_budget(S * P, S, T, sub.B, sub.L, False, False, per)
+        assert budget == _fixed(S * P, S, T, sub.B, sub.L, 0, 0, 0) + per * ((T + 1 + 31) // 32 * 256)
+        pl = plan(S * P, S, T, sub.B, sub.L, list_mode=0, row=2, budget=budget)
+        assert P >= 2 and pl["row_mode"] == 2 and pl["per_chunk"] == per and pl["chunks"] >= 3 and per % P != 0
+        cuts = [r1 for _, r1 in pl["units"][:-1]]
+        assert len(pl["units"]) == pl["chunks"] and any(r % P for r in cuts), (strategy, seed, cuts, P)
+        assert plan(S * P, S, T, sub.B, sub.L, list_mode=0)["chunks"] == 1     # the default budget: one chunk
 
 
 def test_plan_driver_under_asan_and_ubsan():

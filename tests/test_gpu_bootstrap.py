@@ -1,12 +1,16 @@
 """Bootstrap reality check on the GPU (bt_bootstrap / bt_bootstrap_of, k_boot.hip;
 docs/bootstrap_spec.md), every output field bit for bit against the Python-int reference of
 bootstrap_ref.py: the resample path alone on staged increments (every T, L, B, n and group split of
-the staged cases under both row modes, the ends of the range argument by closed form), and the
-walked path on the random cases of random_cases.py and the doubling cycles of limit_cases family A
-(list mode, all-lanes mode, one row per chunk on the arena path, two engines holding half the rows
-each, the raw resampled sums reduced in Python, the refusals).
+the staged cases under both row modes, the ends of the range argument by closed form, groups of
+257 to 600 lanes whose best sum ties at planted lanes), and the walked path on the random cases of
+random_cases.py and the doubling cycles of limit_cases family A (list mode, all-lanes mode, one row
+per chunk on the arena path, all-lanes mode in chunks that cut a row's group, two engines holding
+half the rows each, the raw resampled sums reduced in Python, the refusals), and on ragged rows
+under windows that begin and end at tile edges, at a row's end and one bar before it.
 tests/test_bootstrap_cpu.py holds the host restatement to the same reference and proves that these
-cases reach the plan shapes and outcomes the kernels can get wrong."""
+cases reach the plan shapes and outcomes the kernels can get wrong.
+tests/test_gpu_tstats_boot_limits.py runs the limit families B, C and D; tests/test_gpu_random_lanes.py
+runs the call among the other analysis calls on one engine."""
 import re
 
 import numpy as np
@@ -145,7 +149,80 @@ def test_m1_passes_int64(bare):
     assert got.lane_se().tolist() == [0.0] and got.p_value().tolist() == [0.0]
 
 
+@pytest.mark.parametrize("k", range(len(R.BIG_CASES)))
+def test_staged_groups_above_256_lanes_with_planted_ties(bare, k):
+    """257 to 600 lanes in groups of up to 600, so that a thread of boot_finish_kernel holds up to
+    three lanes; the best row stands twice in a group: at two lanes of one thread, of two threads,
+    at the group's first and last lane. The reference names the lower lane.
+    Measured on an MI355X: below 0.07 s a case, its reference included."""
+    c, want = R.big_case(k), R.big_ref(k)
+    for mode in (1, 2):
+        bare.set_boot_row(mode)
+        try:
+            got = bare.bootstrap_of(c.d, groups=c.sizes, resamples=c.B, block=c.L, seed=c.seed, **OUTS)
+        finally:
+            bare.set_boot_row(0)
+        R.assert_same(got, want, f"n {c.n} groups {c.sizes} ties {c.ties} row mode {mode}")
+    for g, a, _ in c.ties:
+        assert int(got.groups["best_lane"][g]) == a
+
+
 # ------------------------------------------------------------------------ 2. the walked path
+@pytest.mark.parametrize("strategy,seed,name", R.CUT_CASES)
+def test_all_lanes_mode_in_chunks_that_cut_a_group(strategy, seed, name):
+    """All-lanes mode on the arena path under a budget of a third of the lanes a chunk, no multiple
+    of P: rows' groups are cut by chunk boundaries, and a group's row of vmax is completed by two
+    launches. The bytes of the unchunked call and of the reference.
+    Measured on an MI355X: below 0.07 s a case."""
+    c = RC.lane_case(strategy, seed)
+    sub = R.walk_case(strategy, seed)[name]
+    want = R.walk_ref(strategy, seed, name)
+    S, P = len(c.series), c.grid.n_params
+    frm, T = R.window_of(c, sub)
+    per = R.cut_chunk(S, P)
+    with D.Engine(c.grid) as e:
+        _load(e, strategy, c.series, c.ids)
+        call = lambda: e.reality_check(resamples=sub.B, block=sub.L, seed=sub.seed, window=sub.window, per_lane=True, vmax=True)
+        whole = call()
+        e.set_boot_row(2)
+        e.set_boot_budget(R.arena_budget(S * P, S, T, sub.B, sub.L, False, False, per))
+        try:
+            cut = call()
+        finally:
+            e.set_boot_row(0)
+            e.set_boot_budget(0)
+    where = f"{strategy} seed {seed} {name}, {per} of {S * P} lanes a chunk"
+    R.assert_same(cut, want, where, boot=False)
+    assert _bytes(cut, FIELDS[:3]) == _bytes(whole, FIELDS[:3]), f"{where}: not the unchunked call's bytes"
+
+
+@pytest.mark.parametrize("strategy", RC.STRATEGIES)
+def test_window_edges_on_ragged_rows(strategy):
+    """Rows of 1, 2, 64, 65, 130 and 700 bars under windows that begin at 0, 1, 63, 64, 65, 127,
+    128 and 129 and hold 1, 63, 64, 65 and 129 bars: the tile of bar from - 1 is the window's first
+    tile or the one before it, rows end at from, at from + 1 and inside the window, windows end on
+    tile edges. Both row modes, list mode and all-lanes mode, 160 calls.
+    Measured on an MI355X: below 0.07 s a strategy, the 40 references included."""
+    c = R.edge_case(strategy)
+    with D.Engine(c.grid) as e:
+        _load(e, strategy, c.series)
+        for frm in R.EDGE_FROM:
+            for length in R.EDGE_LEN:
+                want = R.edge_ref(strategy, frm, length)
+                kw = dict(resamples=R.EDGE.B, block=R.EDGE.L, seed=R.EDGE.seed + 1000 * frm + length,
+                          window=(frm, frm + length), per_lane=True, vmax=True)
+                for mode in (1, 2):
+                    where = f"{strategy} window [{frm}, {frm + length}) row mode {mode}"
+                    e.set_boot_row(mode)
+                    try:
+                        got = e.reality_check(c.lanes, groups=c.sizes, boot=True, **kw)
+                        every = e.reality_check(**kw)
+                    finally:
+                        e.set_boot_row(0)
+                    R.assert_same(got, want, f"{where}, list mode")
+                    R.assert_same(every, want, f"{where}, all-lanes mode", boot=False)
+
+
 @pytest.mark.parametrize("strategy,seed", [(st, s) for st in RC.STRATEGIES for s in R.WALK_SEEDS])
 def test_walked_cases(strategy, seed):
     c = RC.lane_case(strategy, seed)

@@ -1,9 +1,12 @@
 """Randomised differential suite for the analysis calls on top of a run: replay, walk_forward,
-portfolio, covariance, surface and read_topk on the seeded cases of random_cases.py (random grids,
-ragged rows of the walk / narrow / plateau / spiky paths, shuffled symbol ids, 15 to 115 folds with
-runs of one-bar folds, random portfolio and covariance windows), every output byte for byte against
+portfolio, covariance, trade_stats, reality_check, surface and read_topk on the seeded cases of
+random_cases.py (random grids, ragged rows of the walk / narrow / plateau / spiky paths, shuffled
+symbol ids, 15 to 115 folds with runs of one-bar folds, random portfolio and covariance windows),
+every output byte for byte against
 the references of random_cases.lane_refs: the C oracle's lanes and, from their complete trade lists,
-replay_ref, walkfwd_ref, portfolio_ref, gram_ref, surface_ref and topk_ref.
+replay_ref, walkfwd_ref, portfolio_ref, gram_ref, surface_ref and topk_ref, and against
+tradestats_ref.random_refs and bootstrap_ref.walk_ref (the two calls share the device arena with the
+others; their places in the drawn order come from a generator of their own).
 tests/test_random_lanes_cpu.py holds the host restatements to the same references and proves that
 the default seeds reach the shapes the cases are there for.
 
@@ -15,10 +18,12 @@ import operator
 import numpy as np
 import pytest
 
+import bootstrap_ref as BR
 import dbx_amd as D
 import gram_ref as G
 import portfolio_ref as PR
 import random_cases as RC
+import tradestats_ref as TS
 import walkfwd_ref as R
 from helpers import compare_summary
 from surface_cases import assert_same
@@ -117,14 +122,37 @@ def _covariance(e, c, r, where):
     assert int(cv.sums.sum()) == _i128(book.summary, "s1"), f"{where}: sums against the portfolio's s1"
 
 
+def _trade_stats(e, c, r, where):
+    recs, agg = TS.random_refs(c.strategy, c.seed)
+    ts = e.trade_stats(params=True)
+    TS.assert_same(ts.lanes, recs, f"{where}: trade_stats, all-lanes records")
+    TS.assert_same(ts.params, agg, f"{where}: trade_stats, aggregate")
+    row = {i: s for s, i in enumerate(c.ids)}
+    want = np.array([recs[row[sym], p] for sym, p in c.replay_lanes], D.TSTATS_DTYPE)
+    TS.assert_same(e.trade_stats(c.replay_lanes).lanes, want, f"{where}: trade_stats, list mode")
+
+
+def _reality_check(e, c, r, where):
+    subs = BR.walk_case(c.strategy, c.seed)
+    for name in ("inner",) + (("per_symbol",) if c.seed in BR.WALK_SEEDS else ()):
+        sub = subs[name]
+        got = e.reality_check(BR.sym_lanes(c, sub), groups=sub.sizes, resamples=sub.B, block=sub.L, seed=sub.seed,
+                              window=sub.window, per_lane=True, vmax=True, boot=True)
+        BR.assert_same(got, BR.walk_ref(c.strategy, c.seed, name), f"{where}: reality_check {name}")
+
+
 STEP = {"run": _run_against_oracle, "replay": _replay, "walk_forward": _walk_forward, "portfolio": _portfolio,
-        "covariance": _covariance}
+        "covariance": _covariance, "trade_stats": _trade_stats, "reality_check": _reality_check}
 
 
 @pytest.mark.parametrize("strategy,seed", RC.CASES)
 def test_random_lanes(strategy, seed):
     c, r = RC.lane_case(strategy, seed), RC.lane_refs(strategy, seed)
     where = f"{strategy} seed {seed}"
+    # trade_stats and reality_check at places drawn by a generator of their own, seeded by
+    # strategy and seed: lane_case draws what it always drew
+    order = RC.order_with_later_steps(c)
+    assert sorted(order) == sorted(STEP) and tuple(s for s in order if s in RC.STEPS) == c.order
     with D.Engine(c.grid, topk=c.topk) as e:
         _load(e, c)
         e.run()
@@ -133,12 +161,12 @@ def test_random_lanes(strategy, seed):
         e.set_gram_split(c.gram_split)
         before = (e.summaries().tobytes(), e.read_topk().tobytes())
         wrong = []      # every step runs: a failure names each call that differs, not the first alone
-        for step in c.order:
+        for step in order:
             try:
                 STEP[step](e, c, r, where)
             except AssertionError as err:
                 wrong.append(f"{step}: {err}")
-        assert not wrong, f"{where}, calls in the order {', '.join(c.order)}:\n" + "\n".join(wrong)
+        assert not wrong, f"{where}, calls in the order {', '.join(order)}:\n" + "\n".join(wrong)
         assert (e.summaries().tobytes(), e.read_topk().tobytes()) == before, f"{where}: the run's results changed"
 
 

@@ -3,9 +3,14 @@ every record and aggregate field for field against the Python-int reference of t
 which works from the C oracle's complete trade lists and the curves rebuilt from them: the random
 cases of random_cases.py (all-lanes and list mode, one row per chunk, the identities with the run's
 summaries), ragged rows, the doubling cycles of limit_cases family A (sums of squares past 2^64),
-crafted series that pin the drawdown and streak rules, and the refusals.
+the reduction's geometry (family A repeated to 205 rows: several slices, several chunks, an empty
+trailing slice, sums of squares whose low words wrap between the slices' atomic adds; grids of 100
+and 272 parameters: reduction blocks of 128 and 256 threads, two blocks along p), crafted series
+that pin the drawdown and streak rules, and the refusals.
 tests/test_tradestats_cpu.py holds the host restatements to the same reference and proves that the
-random cases reach the shapes the accounting can get wrong."""
+cases reach the shapes the accounting and the reduction can get wrong.
+tests/test_gpu_tstats_boot_limits.py runs the limit families B, C and D; tests/test_gpu_random_lanes.py
+runs the call among the other analysis calls on one engine."""
 import numpy as np
 import pytest
 
@@ -83,20 +88,12 @@ def test_random_cases(strategy, seed):
 
 
 # ------------------------------------------------------------------------------ 2. ragged rows
-RAGGED = (1, 2, 64, 65, 130, 700)
-RAGGED_GRIDS = {"sma": lambda: D.Grid.sma([1, 3, 10], [2, 20]),
-                "ema_ols": lambda: D.Grid.ema_ols([3, 20], [4, 30], band_bps=5),
-                "boll": lambda: D.Grid.boll([5, 20], [2, 3], [30], [60, 400], k_den=2)}
+RAGGED, RAGGED_GRIDS = T.RAGGED, T.RAGGED_GRIDS   # shared with the window edges of test_gpu_bootstrap.py
 
 
 @pytest.mark.parametrize("strategy", RC.STRATEGIES)
 def test_ragged_rows(strategy):
-    rng = np.random.default_rng([0x7A66, RC.STRATEGIES.index(strategy)])
-    series = []
-    for i, n in enumerate(RAGGED):
-        c = RC._series(rng, n, RC.KINDS[i % 4] if n > 2 else "walk")
-        h, lo = RC._ohlc(rng, c)
-        series.append((h, lo, c))
+    series = T.ragged_series(strategy)
     grid = RAGGED_GRIDS[strategy]()
     recs = T.case_series(strategy, grid, series)
     assert recs["n_bars"][:, 0].tolist() == list(RAGGED) and int(recs["n_trades"].sum()) >= 50
@@ -122,6 +119,43 @@ def test_family_a_doubling_cycles(name):
     T.assert_same(ts.lanes, recs, f"family A {name}: records")
     T.assert_same(ts.params, T.aggregate(recs), f"family A {name}: aggregate")
     assert ts.sq.tolist() == [[T.sq_of(x) for x in r] for r in recs]
+
+
+# --------------------------------------------------------------- 3b. the reduction's geometry
+@pytest.mark.parametrize("name", ("sma", "boll"))
+def test_family_a_many_rows_in_slices_and_chunks(name):
+    """Family A repeated to 205 rows: tstats_agg_kernel with grid y = 4 at the default budget, as
+    chunks of 100, 100 and 5 rows of two slices each, and as chunks of 200 and 5 rows of four slices
+    whose last is empty in the short chunk. The sums of squares wrap 2^64 between the slices' atomic
+    adds (tests/test_tradestats_cpu.py proves it from the reference), so the carry decides sq_hi.
+    Measured on an MI355X, as pytest reports the case with its Python-int aggregates: below 0.07 s."""
+    grid, series, recs = T.family_a_many_rows(name)
+    agg = T.aggregate(recs)
+    with D.Engine(grid) as e:
+        _load(e, name, [(h, lo, c) for c, h, lo in series])
+        for rows in (0,) + T.A_CHUNK_ROWS:
+            where = f"family A {name} x {T.A_ROWS} rows, {rows or 'all'} rows per chunk"
+            e.set_tstats_budget(T.rows_budget(grid.n_params, rows) if rows else 0)
+            try:
+                ts = e.trade_stats(params=True)
+                only = e.trade_stats(per_lane=False, params=True)
+            finally:
+                e.set_tstats_budget(0)
+            T.assert_same(ts.lanes, recs, f"{where}: records")
+            T.assert_same(ts.params, agg, f"{where}: aggregate")
+            assert only.lanes is None
+            T.assert_same(only.params, agg, f"{where}: aggregate alone")
+
+
+@pytest.mark.parametrize("name", list(T.WIDE_GRIDS))
+def test_wide_grids(name):
+    """P = 100 (one reduction block of 128 threads) and P = 272 (two blocks of 256, the second
+    with threads past P) on rows of 65, 130 and 300 bars: both output modes and one row per chunk.
+    Measured on an MI355X: below 0.07 s a case."""
+    grid, series, recs = T.wide_grid_refs(name)
+    with D.Engine(grid) as e:
+        _load(e, "sma", series)
+        _check_all_lanes(e, recs, f"wide grid {name}")
 
 
 # ---------------------------------------------------------------------------- 4. crafted series

@@ -32,19 +32,14 @@ import oracle_np as N
 import orc_ffi as F
 import portfolio_ref as PR
 import walkfwd_ref as R
-from helpers import compare_summary, oracle_row
-from limit_cases import (B_GRIDS, B_TIES, C_GRIDS, CAP_A, CAP_B, CAP_D, D_GRIDS, MAXB, REPS, _a_case, _b_case,
-                         _c_case, _d_case, _oracle)
-from replay_ref import curves_from_trades, curves_from_trades_fast, oracle_lane
+from helpers import compare_summary
+from limit_cases import (B_GRIDS, B_TIES, C_ENGINES, C_GRIDS, CAP_A, CAP_B, CAP_D, D_ENGINES, D_SMA_WIDE, MAXB, REPS,
+                         _a_case, _b_case, _c_lane, _c_rows, _d_rows, _hlc)
+from replay_ref import curves_from_trades, curves_from_trades_fast
 
 WHOLE = 2**31 - 1
 STRATEGIES = ("sma", "ema_ols", "boll")   # family A's cases: ema_ols_128 adds nothing without stages
 TRADE_FIELDS = ("entry_bar", "exit_bar", "side", "entry_px", "exit_px")
-
-
-def _hlc(series):
-    """limit_cases keeps (c, h, l); the references and the loaders below take (h, l, c)."""
-    return [(h, lo, c) for c, h, lo in series]
 
 
 def _load(e, strategy, series):
@@ -357,28 +352,7 @@ def test_b_z_ties_gpu(name):
 
 
 # ----------------------------------------------------------------------------------------- C
-# C_GRIDS as they are, and the longest EMA+OLS window on the EMA series: U = sum k c_k passes 2^64
-C_ENGINES = {**{k: (k, v) for k, v in C_GRIDS.items()}, "ema_ols_8512": ("ema_ols", D_GRIDS["ema_ols"][1])}
 C_WRAP = 1_020_000   # U_t >= 2^64 from about this bar on at w = 8512
-
-
-@functools.lru_cache(None)
-def _c_rows(name):
-    """(strategy, grid, (h, l, c), oracle summaries per param) of one engine of family C."""
-    strategy, mk = C_ENGINES[name]
-    grid, series, oracle = _c_case(strategy)
-    hlc = _hlc(series)[0]
-    if name in C_GRIDS:
-        return strategy, grid, hlc, oracle[0][0]
-    grid = mk()
-    return strategy, grid, hlc, oracle_row(strategy, grid, (hlc[2], hlc[0], hlc[1], hlc[2]), grid.annualization)[0]
-
-
-@functools.lru_cache(2)
-def _c_lane(name, p):
-    """(summary, complete trade list) of one lane: up to 460,745 trades, so only two are kept."""
-    strategy, grid, hlc, rows = _c_rows(name)
-    return oracle_lane(strategy, grid, p, hlc, cap=int(rows[p]["n_trades"]))
 
 
 def test_c_window_sums_wrap_2_64():
@@ -466,23 +440,9 @@ def test_c_single_fold_gpu(name):
 
 
 # ----------------------------------------------------------------------------------------- D
-# D_GRIDS' own SMA lanes have f <= 600: F s stays below 600 * 2^31 * 16192 = 2^54.3. Two more lanes
+# limit_cases.D_ENGINES: D_GRIDS' own SMA lanes have f <= 600: F s stays below 600 * 2^31 * 16192 = 2^54.3. Two more lanes
 # on the same series carry the F s = L f comparison to the top of its range: 2 F = L and 4 F = 3 L
 # at products of 2^58 and 2^58.6 (the walk's comment bounds them by 2^59).
-D_SMA_WIDE = "sma_wide"
-D_ENGINES = list(D_GRIDS) + [D_SMA_WIDE]
-
-
-@functools.lru_cache(None)
-def _d_rows(name):
-    """(strategy, grid, series (c, h, l), oracle rows) of one engine of family D."""
-    if name != D_SMA_WIDE:
-        return _d_case(name)
-    _, _, series, _ = _d_case("sma")
-    grid = D.Grid.sma([8096, 12144], [16192], annualization=98280)
-    return "sma", grid, series, _oracle("sma", grid, series, CAP_D)
-
-
 def test_d_sma_ties_at_the_top_of_the_product_range():
     """Decision bars of the flat series (0-3 ticks of noise under 2^31 - 2^20) with F s == L f
     exactly, the largest of them at a product >= 2^57; the tied bars change no position."""

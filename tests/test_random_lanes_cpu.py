@@ -3,7 +3,8 @@
 references byte for byte, and the proof, from the references alone, that the default seeds reach the
 shapes tests/test_gpu_random_lanes.py is there for: more folds than a wave has lanes with fold 64
 empty on some rows only, 32 fold starts in one tile, stops and targets inside one bar, entry bars
-that cross their own stop, exact SMA ties on the narrow paths."""
+that cross their own stop, exact SMA ties on the narrow paths; and that trade_stats and
+reality_check, which that file puts among the drawn calls, take every place in the order."""
 import numpy as np
 import pytest
 
@@ -110,3 +111,38 @@ def test_default_seeds_use_every_knob_value_and_kind_of_window():
     assert {len(c.cov_lanes) for c in cases} >= {1, 15, 16, 17, 33, 65}
     grams = [RC.lane_refs(c.strategy, c.seed).gram for c in cases]
     assert sum(T > 0 and any(int(x) for x in g.reshape(-1)) for g, _, T in grams) >= 12
+
+
+def test_the_later_steps_take_every_place_among_the_drawn_ones():
+    """test_gpu_random_lanes puts trade_stats and reality_check into a case's drawn order at places
+    of their own drawing (random_cases.order_with_later_steps): over the default seeds each of them runs first, last, directly after
+    every other kind of call, and the two come in both orders. The reference of the sub-case the
+    reality-check step compares on every seed exists for the seeds past bootstrap_ref.WALK_SEEDS too,
+    and the host code agrees with it."""
+    import bootstrap_ref as BR
+    after = {s: set() for s in RC.LATER_STEPS}
+    first, last, both = set(), set(), set()
+    for strategy, seed in RC.CASES:
+        c = RC.lane_case(strategy, seed)
+        order = RC.order_with_later_steps(c)
+        assert order == RC.order_with_later_steps(RC.lane_case.__wrapped__(strategy, seed)), "a function of strategy and seed"
+        assert tuple(s for s in order if s in RC.STEPS) == c.order and sorted(order) == sorted(RC.STEPS + RC.LATER_STEPS)
+        first.add(order[0]), last.add(order[-1])
+        both.add(order.index("trade_stats") < order.index("reality_check"))
+        for s in RC.LATER_STEPS:
+            if order.index(s):
+                after[s].add(order[order.index(s) - 1])
+    if not RC.NS:   # the default seeds
+        assert set(RC.LATER_STEPS) <= first and set(RC.LATER_STEPS) <= last and both == {True, False}
+        assert all(len(v) >= 6 for v in after.values()), after     # each of the six other kinds of call
+    for strategy, seed in RC.CASES:
+        if seed in BR.WALK_SEEDS:       # tests/test_bootstrap_cpu.py holds these
+            continue
+        c, r = RC.lane_case(strategy, seed), RC.lane_refs(strategy, seed)
+        sub = BR.walk_case(strategy, seed)["inner"]
+        eq = np.zeros((len(sub.lanes), max(c.bars)), np.int64)
+        for i, (s, p) in enumerate(sub.lanes):
+            eq[i, :c.bars[s]] = r.curves[s][p][1]
+        got = D.reality_check_host(eq, [c.bars[s] for s, _ in sub.lanes], groups=sub.sizes, resamples=sub.B, block=sub.L,
+                                   seed=sub.seed, window=sub.window, per_lane=True, vmax=True, boot=True)
+        BR.assert_same(got, BR.walk_ref(strategy, seed, "inner"), f"{strategy} seed {seed} inner")

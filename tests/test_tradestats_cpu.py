@@ -126,6 +126,36 @@ def test_family_a_bollinger_passes_int64_in_sq():
     T.assert_same(D.trade_stats_agg_host(got), T.aggregate(recs), "family A, Bollinger: host aggregate")
 
 
+def test_the_vectorised_reference_is_the_loop_s():
+    """lane_stats_fast (numpy, the reference of the rows of 2^22 bars) against lane_stats on every
+    lane of family A and of the default random cases, field for field."""
+    lanes = traded = 0
+    for name in ("sma", "ema_ols", "boll"):
+        _, grid, series, rows = T.LC._a_case(name)
+        _, _, recs = T.family_a_refs(name)
+        fast = np.zeros(recs.shape, D.TSTATS_DTYPE)
+        for s, ((c, _, _), (_, trades)) in enumerate(zip(series, rows)):
+            for p in range(grid.n_params):
+                fast[s, p] = T.as_record(T.lane_stats_fast(trades[p], T.curves_from_trades(c, trades[p])[1]))
+        T.assert_same(fast, recs, f"family A {name}")
+        lanes += recs.size
+    for strategy in RC.STRATEGIES:
+        for seed in SEEDS:
+            r = RC.lane_refs(strategy, seed)
+            recs, _ = T.random_refs(strategy, seed)
+            fast = np.zeros(recs.shape, D.TSTATS_DTYPE)
+            for s in range(recs.shape[0]):
+                for p in range(recs.shape[1]):
+                    fast[s, p] = T.as_record(T.lane_stats_fast(r.lanes[s][p][1], r.curves[s][p][1]))
+            T.assert_same(fast, recs, f"{strategy} seed {seed}")
+            lanes += recs.size
+            traded += int((recs["n_trades"] > 0).sum())
+    assert lanes >= 81 + 36 + 432 + 24 * 6 and traded >= 1000
+    r = T.lane_stats_fast(None, [0, 3, 1])      # no trade: the loop's record too
+    assert r == T.lane_stats([], [0, 3, 1])
+    assert T.longest_run_fast([]) == 0 and T.longest_run_fast([1, 1, 0, 1, 1, 1]) == 3 == T.longest_run([1, 1, 0, 1, 1, 1])
+
+
 def test_reference_on_hand_made_lanes():
     """The rules a reader would check by hand: the tie is not a new peak and ends the run under
     water, of two equal deepest drawdowns the first wins, a flat trade ends both streaks."""
@@ -306,6 +336,71 @@ def test_plan_tstats_on_the_shapes_of_the_issue(plan):
     for args in ((3, 400, 0, 256, 400 * 128), (3, 1 << 20, 0, 256, 100 << 20), (5, 7, 1, 256, 600)):
         pl = plan(*args)
         assert pl["per_chunk"] == 0 and pl["chunks"] == 0 and pl["staging_bytes"] == 0
+
+
+# chunk rows (0: the default budget) -> (chunks, agg_slices, the slices' row ranges chunk by chunk)
+MANY_ROWS_GEOMETRY = {
+    0: (1, 4, [[(0, 52), (52, 104), (104, 156), (156, 205)]]),
+    100: (3, 2, [[(0, 50), (50, 100)], [(0, 50), (50, 100)], [(0, 3), (3, 5)]]),
+    # the short last chunk: ceil(5 / 4) = 2 rows a slice, the fourth begins at row 6 of 5
+    200: (2, 4, [[(0, 50), (50, 100), (100, 150), (150, 200)], [(0, 2), (2, 4), (4, 5), (6, 5)]]),
+}
+# parameters of family A x 205 rows whose slices' low words add up to 2^64 or more, under every one
+# of the three budgets, and the largest such sum in units of 2^64 (rounded down)
+MANY_ROWS_CARRY = {"sma": (7, 2), "boll": (15, 3)}
+
+
+@pytest.mark.parametrize("name", ("sma", "boll"))
+def test_many_rows_reach_several_slices_an_empty_slice_and_the_carry(plan, name):
+    """test_gpu_tradestats.test_family_a_many_rows_in_slices_and_chunks: the plan of each budget,
+    the row range of every slice of every chunk, and that the atomic adds into sq_lo wrap."""
+    grid, series, recs = T.family_a_many_rows(name)
+    R, P = recs.shape
+    assert R == T.A_ROWS == len(series) == 205 and tuple(MANY_ROWS_GEOMETRY) == (0,) + T.A_CHUNK_ROWS
+    for rows, (chunks, slices, ranges) in MANY_ROWS_GEOMETRY.items():
+        pl = plan(R, P, 0, 256, T.rows_budget(P, rows) if rows else 0)
+        assert (pl["per_chunk"], pl["chunks"], pl["agg_slices"]) == (rows or R, chunks, slices) and slices >= 2
+        units = [tuple(u) for u in pl["units"]]
+        assert len(units) == chunks and [T.agg_slice_rows(r1 - r0, slices) for r0, r1 in units] == ranges
+        empty = sum(r0 >= r1 for rr in ranges for r0, r1 in rr)
+        assert empty == (1 if rows == 200 else 0)
+        if rows:
+            assert chunks >= 2 and all(sum(r0 < r1 for r0, r1 in rr) >= 2 for rr in ranges)
+        # the carry: slices' low words that add up to 2^64 or more wrap at some add that meets a
+        # non-zero old value, whatever the order; without the carry sq_hi would be the sum of the
+        # slices' high words alone
+        carried, top = 0, 0
+        for p in range(P):
+            whole = [sum(T.sq_of(x) for x in recs[c0 + r0:c0 + r1, p]) for (c0, _), rr in zip(units, ranges)
+                     for r0, r1 in rr if r0 < r1]
+            low = T.slice_low_words(recs, p, units, slices)
+            assert low == [x & T.M64 for x in whole] and len(low) >= 3
+            if sum(low) >= 2**64:
+                carried += 1
+                top = max(top, sum(low))
+                assert sum(x >> 64 for x in whole) < sum(whole) >> 64 == int(T.aggregate(recs[:, p:p + 1])["sq_hi"][0])
+        assert (carried, top >> 64) == MANY_ROWS_CARRY[name], (rows, carried, top)
+
+
+def test_wide_grids_reach_the_wide_reduction_blocks(plan):
+    """test_gpu_tradestats.test_wide_grids: 128 threads for P = 100, two blocks of 256 for P = 272,
+    whose second block has threads past P; one slice, and three chunks at one row per chunk."""
+    want = {"p100": (100, 128, 1), "p272": (272, 256, 2)}
+    assert set(want) == set(T.WIDE_GRIDS)
+    for name, (P, block, pblocks) in want.items():
+        grid, series, recs = T.wide_grid_refs(name)
+        assert grid.n_params == P == recs.shape[1] and [len(s[2]) for s in series] == [65, 130, 300]
+        pl = plan(3, P)
+        assert (pl["agg_block"], pl["agg_pblocks"], pl["agg_slices"], pl["chunks"]) == (block, pblocks, 1, 1)
+        one = plan(3, P, 0, 256, T.rows_budget(P, 1))
+        assert (one["per_chunk"], one["chunks"], one["agg_block"], one["agg_pblocks"]) == (1, 3, block, pblocks)
+        # every parameter trades on some row, the parameters of the last block included, and the
+        # columns differ (all but one pair): a thread that took another's parameter would show
+        assert (recs["n_trades"].sum(axis=0) > 0).all() and int(recs["n_trades"].sum()) >= 10 * P
+        assert len({recs[:, p].tobytes() for p in range(P)}) >= P - 1
+        if pblocks == 2:
+            assert recs[:, block - 1].tobytes() != recs[:, block].tobytes() != recs[:, 0].tobytes()
+    assert 64 < 100 <= 128 and 272 >= 257 and 272 % 64 == 16 and 2 * 256 - 272 == 240
 
 
 def test_plan_driver_under_asan_and_ubsan():

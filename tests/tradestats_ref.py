@@ -1,8 +1,14 @@
 """Reference for the trade statistics (tests only), from the text of docs/tradestats_spec.md in
 plain Python ints: one lane's record from a complete oracle trade list (closing order) and the
 equity curve of replay_ref.curves_from_trades, the per-parameter aggregate of a record matrix, and
-the references of the shared cases (random_cases.lane_case, limit_cases family A), built once per
-process and not to be modified by a test."""
+the references of the shared cases (random_cases.lane_case, limit_cases family A, the ragged rows,
+family A repeated to many rows, the wide grids), built once per process and not to be modified by a
+test. lane_stats_fast is the same record from numpy arrays, for rows too long for a Python loop;
+tests/test_tradestats_cpu.py pins it to lane_stats field for field.
+
+Also here: the arithmetic of tstats_agg_kernel's slices (agg_slice_rows) and the budget under which
+plan_tstats takes a given number of rows per chunk (rows_budget), restated from the text of plan.h
+and k_tstats.hip; the CPU file holds both to the plan driver."""
 import functools
 
 import numpy as np
@@ -171,3 +177,122 @@ def case_series(strategy, grid, series):
             assert int(summ["n_trades"]) == (0 if tr is None else len(tr))
             recs[s, p] = lane_record(ohlc[2], tr)
     return recs
+
+
+# ------------------------------------------------------------------- the vectorised reference
+def longest_run_fast(flags):
+    """longest_run by differences of the positions where a run begins and ends."""
+    edge = np.diff(np.concatenate([[0], np.asarray(flags, np.int8), [0]]))
+    begin, end = np.flatnonzero(edge == 1), np.flatnonzero(edge == -1)
+    return int((end - begin).max()) if len(begin) else 0
+
+
+def lane_stats_fast(trades, equity):
+    """lane_stats from the oracle's trade array (or None) and the equity array, in numpy: the trade
+    fields in int64 (|pnl| < 2^31 and at most 2^22 trades: no sum leaves int64) with sq summed in
+    Python ints, the drawdown fields from np.maximum.accumulate, the run lengths by
+    longest_run_fast."""
+    E = np.asarray(equity, np.int64)
+    n = 0 if trades is None else len(trades)
+    col = lambda f: trades[f].astype(np.int64) if n else np.zeros(0, np.int64)
+    ebar, xbar, side = col("entry_bar"), col("exit_bar"), col("side")
+    pnl = side * (col("exit_px") - col("entry_px"))
+    hold = xbar - ebar
+    win, loss, lng = pnl > 0, pnl < 0, side > 0
+    w = (ebar | xbar << 31 | lng.astype(np.int64) << 62).astype(np.uint64)
+    z = (w ^ (w >> np.uint64(29))) * np.uint64(0xBF58476D1CE4E5B9)          # uint64: mod 2^64
+    r = {"n_trades": n, "n_win": int(win.sum()), "n_loss": int(loss.sum()), "status": 0,
+         "n_long": int(lng.sum()), "n_long_win": int((lng & win).sum()),
+         "max_win_streak": longest_run_fast(win), "max_loss_streak": longest_run_fast(loss),
+         "hold_sum": int(hold.sum()), "hold_win": int(hold[win].sum()), "hold_max": int(hold.max()) if n else 0,
+         "n_bars": len(E),
+         "gross_win": int(pnl[win].sum()), "gross_loss": int(-pnl[loss].sum()),
+         "max_win": int(pnl[win].max()) if win.any() else 0, "max_loss": int(-pnl[loss].min()) if loss.any() else 0,
+         "sq": sum(x * x for x in pnl.tolist()),
+         "hash": int((z ^ (z >> np.uint64(32))).sum(dtype=np.uint64)) if n else 0}
+    peak = np.maximum.accumulate(np.maximum(E, 0))
+    dd = peak - E
+    r["mdd"] = int(dd.max()) if len(E) else 0
+    if r["mdd"] > 0:
+        r["mdd_bar"] = int(np.argmax(dd))                                   # the first of the maxima
+        r["peak_bar"] = int(np.argmax(E == peak[r["mdd_bar"]]))             # the first bar at that peak
+    else:
+        r["mdd_bar"] = r["peak_bar"] = -1
+    under = E < peak
+    r["underwater_bars"] = int(under.sum())
+    r["max_underwater"] = longest_run_fast(under)
+    return r
+
+
+# ------------------------------------------------------ the reduction's geometry (k_tstats.hip)
+def rows_budget(P, rows):
+    """The staging budget under which plan_tstats takes exactly `rows` dataset rows per chunk
+    (all-lanes mode): agg[P] rounded up to 256 bytes, one rounding of the records, `rows` rows."""
+    return (P * D.TSTATS_AGG_DTYPE.itemsize + 255) // 256 * 256 + 256 + rows * P * D.TSTATS_DTYPE.itemsize
+
+
+def agg_slice_rows(n_rows, slices):
+    """[(r0, r1)] of tstats_agg_kernel's grid y over a chunk of n_rows rows: per = ceil(n_rows /
+    slices) rows each; a slice with r0 >= r1 is empty and returns at once."""
+    per = -(-n_rows // slices)
+    return [(y * per, min(y * per + per, n_rows)) for y in range(slices)]
+
+
+def slice_low_words(recs, p, chunks, slices):
+    """What each non-empty slice of each chunk adds into agg[p].sq_lo: its rows' sum of squares
+    mod 2^64. `chunks`: [(r0, r1)] dataset rows."""
+    out = []
+    for c0, c1 in chunks:
+        for r0, r1 in agg_slice_rows(c1 - c0, slices):
+            if r0 < r1:
+                out.append(sum(sq_of(x) for x in recs[c0 + r0:c0 + r1, p]) & M64)
+    return out
+
+
+A_ROWS = 205          # family A's series repeated cyclically: 4 slices at the default budget
+A_CHUNK_ROWS = (100, 200)   # rows per chunk under the two budgets of the many-row tests
+
+
+@functools.lru_cache(None)
+def family_a_many_rows(name):
+    """(grid, series [(c, h, l)] * A_ROWS, recs A_ROWS x P): row r is series r mod S of family A,
+    and its reference records repeat with it."""
+    grid, series, recs = family_a_refs(name)
+    rows = np.arange(A_ROWS) % len(series)
+    many = recs[rows]
+    many.setflags(write=False)
+    return grid, [series[r] for r in rows], many
+
+
+RAGGED = (1, 2, 64, 65, 130, 700)
+RAGGED_GRIDS = {"sma": lambda: D.Grid.sma([1, 3, 10], [2, 20]),
+                "ema_ols": lambda: D.Grid.ema_ols([3, 20], [4, 30], band_bps=5),
+                "boll": lambda: D.Grid.boll([5, 20], [2, 3], [30], [60, 400], k_den=2)}
+
+
+def ragged_series(strategy, lengths=RAGGED, kinds=RC.KINDS):
+    """[(h, l, c)] of the given lengths, one path kind after the other (seeded by strategy)."""
+    rng = np.random.default_rng([0x7A66, RC.STRATEGIES.index(strategy)])
+    series = []
+    for i, n in enumerate(lengths):
+        c = RC._series(rng, n, kinds[i % len(kinds)] if n > 2 else "walk")
+        h, lo = RC._ohlc(rng, c)
+        series.append((h, lo, c))
+    return series
+
+
+# two SMA grids wider than one 64-thread block of the reduction: 100 parameters (one block of 128
+# threads) and 272 = 4 * 64 + 16 (two blocks of 256, the second with 240 threads past P)
+WIDE_GRIDS = {"p100": lambda: D.Grid.sma(list(range(1, 11)), list(range(12, 52, 4))),
+              "p272": lambda: D.Grid.sma(list(range(1, 18)), list(range(18, 66, 3)))}
+WIDE_ROWS = (65, 130, 300)
+
+
+@functools.lru_cache(None)
+def wide_grid_refs(name):
+    """(grid, series [(h, l, c)], recs 3 x P) of a wide grid on three short ragged rows."""
+    grid = WIDE_GRIDS[name]()
+    series = ragged_series("sma", WIDE_ROWS, ("walk", "spiky"))
+    recs = case_series("sma", grid, series)
+    recs.setflags(write=False)
+    return grid, series, recs
