@@ -16,7 +16,8 @@ from .engine import (ABI_VERSION, FOLD_DTYPE, PIPE_SLOTS, WALKFWD_FOLDS_MAX, WF_
                      merge_portfolios, portfolio_host, walk_forward_lanes, COV_MAX, WIDE_DTYPE, Covariance,
                      covariance_host, TSTATS_AGG_DTYPE, TSTATS_DTYPE, TSTATS_MAX, TradeStats, merge_trade_stats,
                      trade_stats_agg_host, trade_stats_host, BOOT_GROUP_DTYPE, BOOT_LANE_DTYPE, BOOT_MAX,
-                     BOOT_MAX_RESAMPLES, RealityCheck, reality_check_host)
+                     BOOT_MAX_RESAMPLES, RealityCheck, reality_check_host, CSCV_MAX_FOLDS, CSCV_PICKS_MAX)
+from .overfit import CSCV_GROUP_DTYPE, CSCV_PICK_DTYPE, CSCV_RECORDS, Overfit, cscv_combos, cscv_host
 
 __all__ = [
     "ABI_VERSION", "FOLD_DTYPE", "PIPE_SLOTS", "WALKFWD_FOLDS_MAX", "WF_STEP_DTYPE", "WalkForward", "walk_forward_host", "BT_BOLL", "BT_DAILY", "BT_EMA_OLS", "BT_FLAG_PARITY", "BT_FLAG_TIMING", "BT_MINUTE",
@@ -27,5 +28,6 @@ __all__ = [
     "merge_portfolios", "portfolio_host", "walk_forward_lanes", "COV_MAX", "WIDE_DTYPE", "Covariance",
     "covariance_host", "TSTATS_AGG_DTYPE", "TSTATS_DTYPE", "TSTATS_MAX", "TradeStats", "merge_trade_stats",
     "trade_stats_agg_host", "trade_stats_host", "BOOT_GROUP_DTYPE", "BOOT_LANE_DTYPE", "BOOT_MAX",
-    "BOOT_MAX_RESAMPLES", "RealityCheck", "reality_check_host",
+    "BOOT_MAX_RESAMPLES", "RealityCheck", "reality_check_host", "CSCV_GROUP_DTYPE", "CSCV_MAX_FOLDS",
+    "CSCV_PICK_DTYPE", "CSCV_PICKS_MAX", "CSCV_RECORDS", "Overfit", "cscv_combos", "cscv_host",
 ]

@@ -1,11 +1,11 @@
 // analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface, bt_surface_of, bt_topk_of,
-// bt_walk_forward, bt_trade_stats, bt_bootstrap, bt_bootstrap_of, bt_portfolio, bt_covariance and
-// bt_gram_of, with their settings (bt_set_*). This is the list the other files point to. Each
-// call checks its arguments with the pure rules of its header (replay.h, surface.h, topk_rules.h,
-// walkfwd.h, tstats.h, bootstrap.h, portfolio.h, covariance.h), asks plan.h for its chunks and its
-// staging layout, realises that layout in the engine's one arena (engine_state.h), launches, and
-// copies the results back before it returns. Nothing is computed on the CPU but the walk-forward
-// totals (walkfwd.cpp).
+// bt_walk_forward, bt_cscv, bt_cscv_of, bt_trade_stats, bt_bootstrap, bt_bootstrap_of, bt_portfolio,
+// bt_covariance and bt_gram_of, with their settings (bt_set_*). This is the list the other files
+// point to. Each call checks its arguments with the pure rules of its header (replay.h, surface.h,
+// topk_rules.h, walkfwd.h, cscv.h, tstats.h, bootstrap.h, portfolio.h, covariance.h), asks plan.h
+// for its chunks and its staging layout, realises that layout in the engine's one arena
+// (engine_state.h), launches, and copies the results back before it returns. Nothing is computed on
+// the CPU but the walk-forward totals (walkfwd.cpp).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -13,6 +13,7 @@
 
 #include "bootstrap.h"
 #include "covariance.h"
+#include "cscv.h"
 #include "engine_state.h"
 #include "portfolio.h"
 #include "replay.h"
@@ -274,6 +275,98 @@ int32_t walk_forward_impl(bt_engine* e, int32_t K, const int32_t* bounds, int32_
     });
     if (total) walkfwd_totals(S, n_steps, st, e->grid.sqrt_ann, total);
     return 0;
+}
+
+// ---- bt_cscv / bt_cscv_of: the probability of backtest overfitting (k_cscv.hip)
+// The groups go through the device in the chunks of the CscvPlan: per chunk the fold records are
+// walked (bt_cscv: `folds` is NULL, the groups are the dataset's rows) or uploaded (bt_cscv_of) and
+// packed, the group records and histograms zeroed, the combination kernel launched as often as the
+// plan's launch cap asks, and the results copied out. The host adds only what no kernel computes:
+// every group's id and lane count.
+int32_t cscv_run(bt_engine* e, const char* fn, int32_t G, int32_t P, int32_t K, const int32_t* bounds,
+                 const bt_fold* folds, const int32_t* sym_ids, bt_cscv_group* groups, uint32_t* hist,
+                 bt_cscv_pick* picks) {
+    if (G == 0) return 0;
+    const CscvPlan pl = plan_cscv(G, P, K, picks != nullptr, e->walkfwd_budget, e->cscv_work);
+    if (pl.rows_per_chunk < 1)
+        refuse(fn, "one row of P = " + std::to_string(P) + " lanes and K = " + std::to_string(K) + " folds needs " +
+                       std::to_string(pl.row_bytes) + " bytes, above the staging budget of " +
+                       std::to_string(e->walkfwd_budget > 0 ? (size_t)e->walkfwd_budget : kWalkfwdBudget) + " bytes");
+    uint8_t* base = enter(e, pl.staging_bytes);
+    const size_t row_recs = (size_t)K * (size_t)P, H = 2 * (size_t)P - 1, C = (size_t)pl.C;
+    if (bounds)
+        HIPCHK(hipMemcpyAsync(base, bounds, ((size_t)K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, main_stream(e)));
+    HIPCHK(hipMemcpyAsync(base + pl.o_masks, pl.masks.data(), pl.masks.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                          main_stream(e)));
+    WfArgs w{};
+    w.bounds = at<const int32_t>(base, 0);
+    w.rec = at<bt_fold>(base, pl.o_rec);
+    w.P = P, w.K = K;
+    CscvArgs a{};
+    a.rec = w.rec;
+    a.stride_p = folds ? K : 1, a.stride_k = folds ? 1 : P;   // staged [P][K]; the walk's [K][P]
+    a.sums = at<CscvSum>(base, pl.o_sums);
+    a.nret = at<int32_t>(base, pl.o_nret);
+    a.masks = at<const uint32_t>(base, pl.o_masks);
+    a.groups = at<bt_cscv_group>(base, pl.o_groups);
+    a.hist = hist ? at<uint32_t>(base, pl.o_hist) : nullptr;
+    a.picks = picks ? at<bt_cscv_pick>(base, pl.o_picks) : nullptr;
+    a.P = P, a.K = K, a.C = pl.C, a.pairs = pl.pairs;
+    for_chunks((size_t)G, (size_t)pl.rows_per_chunk, [&](size_t r0, size_t m) {
+        a.n_rows = (int32_t)m;
+        if (folds) {
+            HIPCHK(hipMemcpyAsync(w.rec, folds + r0 * row_recs, m * row_recs * sizeof(bt_fold), hipMemcpyHostToDevice,
+                                  main_stream(e)));
+        } else {
+            w.syms = e->d_syms.p + r0;
+            w.n_rows = (int32_t)m;
+            HIPCHK(hipMemsetAsync(w.rec, 0, m * row_recs * sizeof(bt_fold), main_stream(e)));
+            HIPCHK(launch_wf_walk(w, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, main_stream(e)));
+        }
+        HIPCHK(launch_cscv_pack(a, pl, main_stream(e)));
+        HIPCHK(hipMemsetAsync(a.groups, 0, m * sizeof(bt_cscv_group), main_stream(e)));
+        if (hist) HIPCHK(hipMemsetAsync(a.hist, 0, m * H * sizeof(uint32_t), main_stream(e)));
+        for_chunks(m, (size_t)pl.rows_per_launch, [&](size_t l0, size_t rows) {
+            for_chunks((size_t)pl.pairs, (size_t)pl.pairs_per_launch, [&](size_t q0, size_t nq) {
+                HIPCHK(launch_cscv(a, pl, (int32_t)l0, (int32_t)rows, (int64_t)q0, (int64_t)(q0 + nq), e->grid.sqrt_ann,
+                                   main_stream(e)));
+            });
+        });
+        bt_cscv_group* g = groups ? groups + r0 : nullptr;
+        if (g) HIPCHK(hipMemcpyAsync(g, a.groups, m * sizeof(bt_cscv_group), hipMemcpyDeviceToHost, main_stream(e)));
+        if (hist) HIPCHK(hipMemcpyAsync(hist + r0 * H, a.hist, m * H * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream(e)));
+        if (picks)
+            HIPCHK(hipMemcpyAsync(picks + r0 * C, a.picks, m * C * sizeof(bt_cscv_pick), hipMemcpyDeviceToHost, main_stream(e)));
+        HIPCHK(hipStreamSynchronize(main_stream(e)));
+        if (g)
+            for (size_t r = 0; r < m; ++r) {
+                g[r].sym = folds ? (sym_ids ? sym_ids[r0 + r] : (int32_t)(r0 + r)) : e->syms[r0 + r].id;
+                g[r].n_lanes = P;
+            }
+    });
+    return 0;
+}
+
+int32_t cscv_impl(bt_engine* e, int32_t K, const int32_t* bounds, bt_cscv_group* groups, uint32_t* hist,
+                  bt_cscv_pick* picks) {
+    const char* fn = "bt_cscv";
+    if (!e) refuse(fn, "null engine");
+    if (e->syms.empty()) refuse(fn, "no dataset loaded");
+    if (K >= 1 && !bounds) refuse(fn, "bounds are required");
+    const int32_t S = (int32_t)e->syms.size();
+    const std::string why = cscv_refusal(K, bounds, groups != nullptr, hist != nullptr, picks != nullptr, S);
+    if (!why.empty()) refuse(fn, why);
+    return cscv_run(e, fn, S, e->P, K, bounds, nullptr, nullptr, groups, hist, picks);
+}
+
+int32_t cscv_of_impl(bt_engine* e, int32_t G, int32_t P, int32_t K, const bt_fold* folds, const int32_t* sym_ids,
+                     bt_cscv_group* groups, uint32_t* hist, bt_cscv_pick* picks) {
+    const char* fn = "bt_cscv_of";
+    if (!e) refuse(fn, "null engine");
+    std::string why = cscv_refusal(K, nullptr, groups != nullptr, hist != nullptr, picks != nullptr, std::max(G, 0));
+    if (why.empty()) why = cscv_folds_refusal(G, P, K, folds);
+    if (!why.empty()) refuse(fn, why);
+    return cscv_run(e, fn, G, P, K, nullptr, folds, sym_ids, groups, hist, picks);
 }
 
 // ---- bt_trade_stats: every lane's, or chosen lanes', trade statistics (k_tstats.hip)
@@ -613,6 +706,20 @@ int32_t bt_walk_forward(bt_engine* e, int32_t K, const int32_t* bounds, int32_t 
 
 int32_t bt_set_walkfwd_budget(bt_engine* e, int64_t bytes) {
     ABI_GUARD(-1, { return set_knob(e, "bt_set_walkfwd_budget", "bytes", bytes, -1, &EngineState::walkfwd_budget); })
+}
+
+int32_t bt_cscv(bt_engine* e, int32_t K, const int32_t* bounds, bt_cscv_group* groups, uint32_t* hist,
+                bt_cscv_pick* picks) {
+    ABI_GUARD(-1, { return cscv_impl(e, K, bounds, groups, hist, picks); })
+}
+
+int32_t bt_cscv_of(bt_engine* e, int32_t G, int32_t P, int32_t K, const bt_fold* folds, const int32_t* sym_ids,
+                   bt_cscv_group* groups, uint32_t* hist, bt_cscv_pick* picks) {
+    ABI_GUARD(-1, { return cscv_of_impl(e, G, P, K, folds, sym_ids, groups, hist, picks); })
+}
+
+int32_t bt_set_cscv_work(bt_engine* e, int64_t cells) {
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_cscv_work", "cells", cells, -1, &EngineState::cscv_work); })
 }
 
 int32_t bt_trade_stats(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstats* out, bt_tstats_agg* agg) {

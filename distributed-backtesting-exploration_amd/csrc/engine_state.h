@@ -111,6 +111,7 @@ struct EngineState {
     int32_t surface_chunks = 0;    // bt_set_surface_chunks (0 = the planner's choice)
     PinnedBuf<uint8_t> h_surface;  // the results of one reduction
     int64_t walkfwd_budget = 0;    // bt_set_walkfwd_budget (0 = kWalkfwdBudget)
+    int64_t cscv_work = 0;         // bt_set_cscv_work (0 = kCscvWork)
     int64_t tstats_budget = 0;     // bt_set_tstats_budget (0 = kTstatsBudget)
     int64_t boot_budget = 0;       // bt_set_boot_budget (0 = kBootBudget)
     int32_t boot_row = 0;          // bt_set_boot_row (0 = the planner's choice, 1 = LDS, 2 = arena)

@@ -1,12 +1,14 @@
 // host_common.h — what the host rule files of the analysis calls (surface.cpp, walkfwd.cpp,
-// tstats.cpp, bootstrap.cpp, portfolio.cpp, covariance.cpp) and analysis.cpp share: the one error
-// path of a HIP-free entry point, the int128 word helpers and the rules of replayed curves and
-// staged increments. No HIP include: a plain host compiler builds it (the drivers under
+// cscv.cpp, tstats.cpp, bootstrap.cpp, portfolio.cpp, covariance.cpp) and analysis.cpp share: the
+// one error path of a HIP-free entry point, the int128 word helpers, the host Sharpe of fold
+// sums and the rules of replayed curves and staged increments. No HIP include: a plain host compiler builds it (the drivers under
 // tests/asan); internal.h includes it, so the word helpers serve the kernels too.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -38,6 +40,30 @@ BT_HD inline uint64_t wide_lo(i128 x) { return (uint64_t)x; }
 BT_HD inline int64_t wide_hi(i128 x) { return (int64_t)(x >> 64); }
 BT_HD inline void wide_split(i128 x, uint64_t& lo, int64_t& hi) { lo = wide_lo(x), hi = wide_hi(x); }
 BT_HD inline bt_wide wide_rec(i128 x) { return bt_wide{wide_lo(x), wide_hi(x)}; }
+
+// The engine's orderable Sharpe (oracle spec §5) on the host: the double's bits, monotone as an
+// unsigned integer.
+inline uint64_t host_sharpe_key(double x) {
+    uint64_t u;
+    memcpy(&u, &x, sizeof u);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
+}
+
+// walkforward_spec §4's Sharpe of the sums over n return bars (0 when there are none), with the
+// compiler's int128: the conversion of the sums rounds to nearest, ties to even.
+inline double host_sharpe(i128 s1, i128 s2, int64_t n, double sqrt_ann) {
+    if (n < 1) return 0.0;
+    const double nn = (double)n;
+    const double m = std::ldexp((double)s1, -56) / nn;
+    const double mm = m * m;
+    const double v = std::ldexp((double)s2, -56) / nn - mm;
+    return v > 0 ? (m / std::sqrt(v)) * sqrt_ann : 0.0;
+}
+
+// Return bars of a fold record: its bars but bar 0.
+inline int64_t fold_ret_bars(const bt_fold& f) {
+    return (int64_t)f.n_bars - (f.first_bar == 0 && f.n_bars > 0 ? 1 : 0);
+}
 
 // d[n][T] of a staged call (bt_gram_of, bt_bootstrap_of) against |d| < 2^31.
 inline std::string increments_domain_refusal(int64_t n, int64_t T, const int32_t* d) {

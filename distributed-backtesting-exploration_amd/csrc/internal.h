@@ -190,6 +190,37 @@ hipError_t launch_wf_walk(const WfArgs& a, const int32_t* high, const int32_t* l
                           const Grid& g, hipStream_t st);
 hipError_t launch_wf_select(const WfArgs& a, const Grid& g, const WalkfwdPlan& pl, hipStream_t st);
 
+// Probability of backtest overfitting (k_cscv.hip, bt_cscv / bt_cscv_of; docs/cscv_spec.md) of one
+// chunk of groups. The pack (one thread per (row, lane)) reads the s1/s2 words of the chunk's fold
+// records, fold k of lane p of a row at rec[row * K * P + p * stride_p + k * stride_k], and leaves
+// per lane K + 1 CscvSum (its folds, then their total) and per row its K return-bar counts. The
+// combination kernel (one thread per combination pair, grid y = the launch's rows) adds to the
+// group records and the histograms, which the host zeroes before a chunk's first launch, and
+// stores the picks.
+struct alignas(32) CscvSum {
+    uint64_t s1_lo;
+    int64_t s1_hi;
+    uint64_t s2_lo;
+    int64_t s2_hi;
+};
+struct CscvArgs {
+    const bt_fold* rec;
+    int64_t stride_p, stride_k;
+    CscvSum* sums;                 // [n_rows][P][K + 1]
+    int32_t* nret;                 // [n_rows][K]
+    const uint32_t* masks;         // [pairs]
+    bt_cscv_group* groups;         // [n_rows]
+    uint32_t* hist;                // [n_rows][2P - 1] or nullptr
+    bt_cscv_pick* picks;           // [n_rows][C] or nullptr
+    int32_t n_rows, P, K;
+    int64_t C, pairs;
+};
+struct CscvPlan;
+hipError_t launch_cscv_pack(const CscvArgs& a, const CscvPlan& pl, hipStream_t st);
+// rows [row0, row0 + rows) of the chunk, pairs [q0, q1) of each
+hipError_t launch_cscv(const CscvArgs& a, const CscvPlan& pl, int32_t row0, int32_t rows, int64_t q0, int64_t q1,
+                       double sqrt_ann, hipStream_t st);
+
 // Trade statistics (k_tstats.hip, bt_trade_stats; docs/tradestats_spec.md) of one chunk. The walk
 // (one wave64 workgroup per lane) leaves one bt_tstats per lane: with `lanes` the n staged
 // requests in order, else lane row * P + param of the chunk's n_rows dataset rows. The reduction

@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "batch.h"
+#include "cscv.h"
 #include "csv.h"
 #include "lds_layout.h"
 
@@ -471,6 +472,69 @@ WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int 
     pl.staging_bytes = rows > 0 ? fixed + (size_t)rows * pl.row_bytes : 0;
     pl.o_rec = c.take((size_t)rows * rec_bytes);
     pl.o_steps = c.take((size_t)rows * step_bytes);
+    return pl;
+}
+
+// --------------------------------------------------------------------------- overfitting (CSCV)
+std::vector<uint32_t> cscv_masks(int32_t K) {
+    std::vector<uint32_t> m;
+    if (K < 2 || K > BT_CSCV_MAX_FOLDS || K % 2) return m;
+    const int64_t pairs = cscv_combos(K) / 2;
+    m.reserve((size_t)pairs);
+    uint32_t v = (1u << (K / 2)) - 1;              // the smallest word with K/2 bits
+    for (int64_t q = 0; q < pairs; ++q) {
+        m.push_back(v);
+        const uint32_t c = v & (0u - v), r = v + c;   // Gosper: the next word with as many bits
+        v = (((r ^ v) >> 2) / c) | r;
+    }
+    return m;
+}
+
+CscvPlan plan_cscv(int32_t G, int32_t P, int32_t K, bool want_picks, int64_t budget_req, int64_t work_req) {
+    CscvPlan pl{};
+    G = std::max(G, 0);
+    P = std::max(P, 1);
+    K = std::min(std::max(K, 2), BT_CSCV_MAX_FOLDS) & ~1;
+    pl.masks = cscv_masks(K);
+    pl.C = cscv_combos(K);
+    pl.pairs = pl.C / 2;
+    pl.block = (int32_t)std::min<int64_t>(256, (pl.pairs + 63) / 64 * 64);
+    pl.pack_block = 64 * std::min((P + 63) / 64, 4);
+    const size_t budget = budget_req > 0 ? (size_t)budget_req : kWalkfwdBudget;
+    const int64_t work = work_req > 0 ? work_req : kCscvWork;
+    Carve c;
+    c.take(((size_t)K + 1) * sizeof(int32_t));     // the bounds, at 0
+    pl.bounds_bytes = c.end;
+    pl.o_masks = c.take((size_t)pl.pairs * sizeof(uint32_t));
+    const size_t rec_bytes = (size_t)K * (size_t)P * sizeof(bt_fold), sum_bytes = (size_t)P * ((size_t)K + 1) * 32,
+                 nret_bytes = (size_t)K * sizeof(int32_t), hist_bytes = (2 * (size_t)P - 1) * sizeof(uint32_t),
+                 pick_bytes = want_picks ? (size_t)pl.C * sizeof(bt_cscv_pick) : 0;
+    pl.row_bytes = rec_bytes + sum_bytes + nret_bytes + sizeof(bt_cscv_group) + hist_bytes + pick_bytes;
+    // each of the six row regions rounds up by less than kStagingAlign
+    const size_t fixed = c.end + 6 * kStagingAlign;
+    int64_t rows = budget > fixed ? (int64_t)((budget - fixed) / pl.row_bytes) : 0;
+    rows = std::min<int64_t>(rows, (1LL << 30) / P);   // one grid index per lane of a chunk (walk, pack)
+    rows = std::min<int64_t>(rows, G);
+    pl.rows_per_chunk = (int32_t)rows;
+    pl.chunks = rows > 0 ? (int32_t)((G + rows - 1) / rows) : 0;
+    const int64_t row_cells = pl.pairs * P;
+    if (row_cells <= work) {
+        pl.rows_per_launch = (int32_t)std::min<int64_t>(work / row_cells, kCscvMaxRowsPerLaunch);
+        pl.pairs_per_launch = pl.pairs;
+    } else {
+        pl.rows_per_launch = 1;
+        int64_t q = std::max<int64_t>(work / P, 1);
+        if (q > pl.block) q -= q % pl.block;
+        pl.pairs_per_launch = q;
+    }
+    pl.launches_per_row = (int32_t)((pl.pairs + pl.pairs_per_launch - 1) / pl.pairs_per_launch);
+    pl.staging_bytes = rows > 0 ? fixed + (size_t)rows * pl.row_bytes : 0;
+    pl.o_rec = c.take((size_t)rows * rec_bytes);
+    pl.o_sums = c.take((size_t)rows * sum_bytes);
+    pl.o_nret = c.take((size_t)rows * nret_bytes);
+    pl.o_groups = c.take((size_t)rows * sizeof(bt_cscv_group));
+    pl.o_hist = c.take((size_t)rows * hist_bytes);
+    pl.o_picks = c.take((size_t)rows * pick_bytes);
     return pl;
 }
 

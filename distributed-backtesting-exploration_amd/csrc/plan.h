@@ -141,6 +141,37 @@ struct WalkfwdPlan {
 // `budget_req`: bt_set_walkfwd_budget (0 = kWalkfwdBudget).
 WalkfwdPlan plan_walkfwd(int32_t S, int32_t P, int32_t K, int32_t max_bars, int cus, int64_t budget_req = 0);
 
+// What a probability of backtest overfitting (k_cscv.hip, bt_cscv / bt_cscv_of) of G groups x P
+// lanes x K folds is launched with. C = binom(K, K/2) combinations in `pairs` = C / 2 pairs (c,
+// C - 1 - c), one thread each: masks[q] is combination q's K-bit word (bit K - 1 clear), in
+// increasing numeric order. The groups go through the device in chunks of rows_per_chunk whole
+// rows (the last one shorter), bounded by the walk-forward budget: per row its fold records (the
+// walk's [K][P] or a staged call's [P][K]), the packed sums [P][K + 1] (a lane's K folds, then its
+// total), the K return-bar counts, the group record, the histogram and, when asked for, C picks.
+// rows_per_chunk == 0: one row alone does not fit, and the call is refused. A chunk is cut into
+// launches of at most `work` cells, a cell being one (row, pair, lane): rows_per_launch whole rows
+// with every pair while a row has at most `work` cells, else one row and pairs_per_launch pairs
+// (a multiple of the block above one block), so that no single kernel runs long.
+constexpr int64_t kCscvWork = 6000000000LL;    // 0.22 s at the measured rate: profiles/cscv/README.md
+constexpr int32_t kCscvMaxRowsPerLaunch = 65535;   // grid y
+struct CscvPlan {
+    int64_t C, pairs;
+    std::vector<uint32_t> masks;   // [pairs]
+    int32_t block;                 // threads of a combination block (a multiple of 64, at most 256)
+    int32_t rows_per_chunk, chunks;
+    int32_t rows_per_launch;       // whole rows per launch (1 when a row is cut)
+    int64_t pairs_per_launch;      // pairs of a row per launch (`pairs` when rows are whole)
+    int32_t launches_per_row;      // ceil(pairs / pairs_per_launch)
+    int32_t pack_block;            // threads of a pack block (one thread per (row, lane) of a chunk)
+    size_t bounds_bytes, row_bytes;
+    size_t o_masks, o_rec, o_sums, o_nret, o_groups, o_hist, o_picks;   // the bounds lie at 0
+    size_t staging_bytes;          // of a full chunk (0 with rows_per_chunk == 0)
+};
+// The first C / 2 K-bit words with K / 2 bits set, ascending (Gosper's hack); K even in [2, 20].
+std::vector<uint32_t> cscv_masks(int32_t K);
+// `budget_req`: bt_set_walkfwd_budget (0 = kWalkfwdBudget); `work_req`: bt_set_cscv_work (0 = kCscvWork).
+CscvPlan plan_cscv(int32_t G, int32_t P, int32_t K, bool want_picks, int64_t budget_req = 0, int64_t work_req = 0);
+
 // What the trade statistics (k_tstats.hip, bt_trade_stats) are launched with. The units of a call
 // are dataset rows of P lanes each (all-lanes mode) or requested lanes (list mode), processed in
 // chunks of per_chunk (the last one shorter): chunk c holds units [c * per_chunk, min(units,

@@ -44,26 +44,10 @@ using bt::refuse;
 using bt::wide_join;
 using bt::wide_split;
 
-// The engine's orderable Sharpe (spec §5): the double's bits, monotone as an unsigned integer.
-uint64_t sharpe_key(double x) {
-    uint64_t u;
-    memcpy(&u, &x, sizeof u);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
-}
-
-// Spec §4's Sharpe of the sums over n return bars (0 when there are none). The conversion of the
-// int128 sums rounds to nearest, ties to even.
-double sharpe_of(i128 s1, i128 s2, int64_t n, double sqrt_ann) {
-    if (n < 1) return 0.0;
-    const double nn = (double)n;
-    const double m = std::ldexp((double)s1, -56) / nn;
-    const double mm = m * m;
-    const double v = std::ldexp((double)s2, -56) / nn - mm;
-    return v > 0 ? (m / std::sqrt(v)) * sqrt_ann : 0.0;
-}
-
-// Return bars of a fold record: its bars but bar 0.
-int64_t n_ret(const bt_fold& f) { return (int64_t)f.n_bars - (f.first_bar == 0 && f.n_bars > 0 ? 1 : 0); }
+// The shared host Sharpe, its key and a record's return bars (host_common.h).
+uint64_t sharpe_key(double x) { return bt::host_sharpe_key(x); }
+double sharpe_of(i128 s1, i128 s2, int64_t n, double sqrt_ann) { return bt::host_sharpe(s1, s2, n, sqrt_ann); }
+int64_t n_ret(const bt_fold& f) { return bt::fold_ret_bars(f); }
 
 bt_fold empty_fold(int32_t first_bar) {
     bt_fold f;

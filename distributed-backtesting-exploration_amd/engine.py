@@ -179,6 +179,7 @@ _LATE_SYMBOLS = {
     "bt_set_walkfwd_budget": (3, [C.c_void_p, C.c_int64], C.c_int32),
     "bt_walk_forward_host": (3, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_void_p], C.c_int32),
+    "bt_set_cscv_work": (3, [C.c_void_p, C.c_int64], C.c_int32),
     "bt_portfolio": (3, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                          C.c_void_p, C.c_void_p], C.c_int32),
     "bt_set_portfolio_replicas": (3, [C.c_void_p, C.c_int32], C.c_int32),
@@ -1147,6 +1148,25 @@ class Engine:
         """Device staging budget of walk_forward in bytes: 0 = the default (256 MB). Results are
         identical whatever the budget."""
         _check(sym("bt_set_walkfwd_budget")(self._h, nbytes))
+
+    # ---- probability of backtest overfitting (overfit.py, k_cscv.hip)
+    def cscv(self, bounds=None, folds=None, sym_ids=None, hist: bool = True, picks: bool = False):
+        """Combinatorially symmetric cross-validation (docs/cscv_spec.md): with `bounds` (K + 1 bar
+        indices, K even in [2, CSCV_MAX_FOLDS]) every lane of the resident dataset is walked and cut
+        into K folds as walk_forward cuts it, every symbol being one group of n_params lanes; with
+        `folds` (FOLD_DTYPE[G, P, K], for example WalkForward.folds, and optionally sym_ids[G]) the
+        same kernels run on those records. Per group, every way of taking K/2 folds as the in-sample
+        half picks the lane with the best in-sample Sharpe and ranks it on the other half.
+        Overfit.pbo() is the share of combinations whose pick ranks in the lower half there. With
+        picks every combination's pick comes back (at most CSCV_PICKS_MAX records). The call, its
+        records and its result type live in overfit.py."""
+        from .overfit import engine_cscv
+        return engine_cscv(self, bounds, folds, sym_ids, hist, picks)
+
+    def set_cscv_work(self, cells: int) -> None:
+        """The most (row, combination pair, lane) cells one launch of cscv covers: 0 = the default.
+        Results are identical whatever the value."""
+        _check(sym("bt_set_cscv_work")(self._h, cells))
 
     # ---- trade statistics and drawdown timing (bt_trade_stats, k_tstats.hip)
     def trade_stats(self, lanes=None, per_lane: bool = True, params: bool = False) -> TradeStats:

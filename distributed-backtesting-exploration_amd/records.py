@@ -21,6 +21,8 @@ COV_MAX = 2048  # BT_COV_MAX: lanes per Engine.covariance call
 TSTATS_MAX = 1 << 20  # BT_TSTATS_MAX: lanes per Engine.trade_stats call in list mode
 BOOT_MAX = 1 << 20  # BT_BOOT_MAX: lanes per call with a lane list, and of bootstrap_of
 BOOT_MAX_RESAMPLES = 65536  # BT_BOOT_MAX_RESAMPLES
+CSCV_MAX_FOLDS = 20  # BT_CSCV_MAX_FOLDS: folds of Engine.cscv (even, at least 2)
+CSCV_PICKS_MAX = 1 << 22  # pick records Engine.cscv(picks=True) returns
 
 SUMMARY_DTYPE = np.dtype([
     ("n_trades", "<i4"), ("status", "<i4"), ("pnl", "<i8"), ("mdd", "<i8"),

@@ -556,6 +556,56 @@ int32_t bt_bootstrap_host(int32_t n, const int64_t* equity, const int32_t* n_bar
                           const int32_t* goff, int32_t from_bar, int32_t to_bar, int32_t B, int32_t L,
                           uint64_t seed, bt_boot_group* groups_out, bt_boot_lane* lanes_out, int64_t* vmax_out,
                           int64_t* boot_out);
+/* ---- probability of backtest overfitting (k_cscv.hip, cscv.cpp; semantics: docs/cscv_spec.md).
+ * How often does "pick the best lane in-sample" choose a lane that is below the median out of
+ * sample? Combinatorially symmetric cross-validation over the fold records of bt_walk_forward: the
+ * series is cut into K folds (K even, 2 <= K <= BT_CSCV_MAX_FOLDS) by bounds[K + 1] as there, and
+ * every one of the C = binom(K, K/2) ways of taking K/2 folds as the in-sample half is a
+ * combination; combination c has the c-th K-bit mask with K/2 bits set in increasing numeric order
+ * (bit k = fold k in-sample). A group is one dataset row's P lanes. Per group and combination the
+ * lane p* with the largest in-sample Sharpe (exact int128 sums over the half's folds, ties to the
+ * lowest p) is ranked among the group's lanes on the other half: r2 = 2 * #{below} + #{equal, not
+ * p*} in [0, 2(P-1)]. The combination is overfit when r2 <= P - 1, a loss when p*'s out-of-sample
+ * sum of returns is negative, tied when another lane shares p*'s in-sample Sharpe, and dead (no
+ * pick, counted in n_dead only) when either half has no return bar.
+ *   groups [G]          one bt_cscv_group per row (G = S), or NULL;
+ *   hist   [G][2P - 1]  live combinations per r2, or NULL;
+ *   picks  [G][C]       one bt_cscv_pick per combination (lane -1 when dead), or NULL; G*C <= 2^22.
+ * Every figure is an integer or one Sharpe double: nothing depends on chunking or launch splitting.
+ * Synchronous like bt_walk_forward, whose row chunks and staging budget (bt_set_walkfwd_budget) it
+ * uses; bt_run need not have been called and nothing another entry point reads changes. Added
+ * within ABI 3 (additive). Returns 0, or -1 with bt_last_error naming the offending value (the
+ * engine stays usable): a null engine, no dataset, K odd or outside [2, 20], bounds as in
+ * bt_walk_forward, all three outputs NULL, picks with G*C > 2^22, one row larger than the budget. */
+#define BT_CSCV_MAX_FOLDS 20
+typedef struct bt_cscv_group {        /* 32 bytes */
+    int32_t sym, n_lanes;             /* the row's global id (staged: sym_ids[g], or g); P */
+    int32_t n_live, n_dead;           /* combinations with a pick; without: n_live + n_dead = C */
+    int32_t n_overfit, n_loss, n_tied;
+    int32_t pad;
+} bt_cscv_group;
+typedef struct bt_cscv_pick {         /* 24 bytes */
+    int32_t lane, r2;                 /* p* (-1: dead), its out-of-sample rank r2 */
+    double  is_sharpe, oos_sharpe;    /* p*'s Sharpe on the in-sample and on the other half */
+} bt_cscv_pick;
+int32_t bt_cscv(bt_engine* e, int32_t K, const int32_t* bounds /* K + 1 */, bt_cscv_group* groups,
+                uint32_t* hist, bt_cscv_pick* picks);
+/* The same kernels on a caller's fold records folds[G][P][K] (for example the folds of
+ * bt_walk_forward): G groups of P lanes. Only first_bar, n_bars and the s1/s2 words of a record
+ * are read. sym_ids[G] or NULL (then group g reports sym = g). Works on any engine (also one
+ * without a dataset). Also refused: P < 1, G < 0 (G == 0 writes nothing), NULL folds with G > 0, a
+ * group whose lanes disagree in first_bar or n_bars of some fold (group, lane and fold are named),
+ * first_bar or n_bars below 0 or a group of 2^31 - 1 return bars or more, and a record with s2 < 0,
+ * s2 >= 2^120 or |s1| >= 2^120 (so that 20 of them stay inside an int128). */
+int32_t bt_cscv_of(bt_engine* e, int32_t G, int32_t P, int32_t K, const bt_fold* folds,
+                   const int32_t* sym_ids, bt_cscv_group* groups, uint32_t* hist, bt_cscv_pick* picks);
+/* Host, no GPU needed: the scalar restatement. annualization is bt_config.annualization. */
+int32_t bt_cscv_host(int32_t G, int32_t P, int32_t K, const bt_fold* folds, const int32_t* sym_ids,
+                     int64_t annualization, bt_cscv_group* groups, uint32_t* hist, bt_cscv_pick* picks);
+/* The most (row, combination pair, lane) cells one launch of the combination kernel covers: 0 =
+ * the default. A chunk is cut into launches of whole rows or, where one row has more, of a row's
+ * pairs. Results are identical whatever the value (tests force many launches with a small one). */
+int32_t bt_set_cscv_work(bt_engine* e, int64_t cells);
 /* Average device time of the dominant kernel (BT_FLAG_TIMING), and how many launches. */
 int32_t bt_kernel_timing(bt_engine* e, double* total_ms, int64_t* launches, const char** name);
 int32_t bt_reset_timing(bt_engine* e);
