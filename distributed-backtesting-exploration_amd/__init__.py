@@ -18,6 +18,8 @@ from .engine import (ABI_VERSION, FOLD_DTYPE, PIPE_SLOTS, WALKFWD_FOLDS_MAX, WF_
                      trade_stats_agg_host, trade_stats_host, BOOT_GROUP_DTYPE, BOOT_LANE_DTYPE, BOOT_MAX,
                      BOOT_MAX_RESAMPLES, RealityCheck, reality_check_host, CSCV_MAX_FOLDS, CSCV_PICKS_MAX)
 from .overfit import CSCV_GROUP_DTYPE, CSCV_PICK_DTYPE, CSCV_RECORDS, Overfit, cscv_combos, cscv_host
+from .costs import (COST_AGG_DTYPE, COST_BPS_MAX, COST_DTYPE, COST_FIXED_MAX, COST_LEVELS_MAX, COST_RECORDS, COSTS_MAX,
+                    Costs, costs_agg_host, costs_host, merge_costs)
 
 __all__ = [
     "ABI_VERSION", "FOLD_DTYPE", "PIPE_SLOTS", "WALKFWD_FOLDS_MAX", "WF_STEP_DTYPE", "WalkForward", "walk_forward_host", "BT_BOLL", "BT_DAILY", "BT_EMA_OLS", "BT_FLAG_PARITY", "BT_FLAG_TIMING", "BT_MINUTE",
@@ -30,4 +32,6 @@ __all__ = [
     "trade_stats_agg_host", "trade_stats_host", "BOOT_GROUP_DTYPE", "BOOT_LANE_DTYPE", "BOOT_MAX",
     "BOOT_MAX_RESAMPLES", "RealityCheck", "reality_check_host", "CSCV_GROUP_DTYPE", "CSCV_MAX_FOLDS",
     "CSCV_PICK_DTYPE", "CSCV_PICKS_MAX", "CSCV_RECORDS", "Overfit", "cscv_combos", "cscv_host",
+    "COST_AGG_DTYPE", "COST_BPS_MAX", "COST_DTYPE", "COST_FIXED_MAX", "COST_LEVELS_MAX", "COST_RECORDS", "COSTS_MAX",
+    "Costs", "costs_agg_host", "costs_host", "merge_costs",
 ]

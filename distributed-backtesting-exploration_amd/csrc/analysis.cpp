@@ -1,9 +1,9 @@
 // analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface, bt_surface_of, bt_topk_of,
-// bt_walk_forward, bt_cscv, bt_cscv_of, bt_trade_stats, bt_bootstrap, bt_bootstrap_of, bt_portfolio,
-// bt_covariance and bt_gram_of, with their settings (bt_set_*). This is the list the other files
-// point to. Each call checks its arguments with the pure rules of its header (replay.h, surface.h,
-// topk_rules.h, walkfwd.h, cscv.h, tstats.h, bootstrap.h, portfolio.h, covariance.h), asks plan.h
-// for its chunks and its staging layout, realises that layout in the engine's one arena
+// bt_walk_forward, bt_cscv, bt_cscv_of, bt_trade_stats, bt_costs, bt_bootstrap, bt_bootstrap_of,
+// bt_portfolio, bt_covariance and bt_gram_of, with their settings (bt_set_*). This is the list the
+// other files point to. Each call checks its arguments with the pure rules of its header (replay.h,
+// surface.h, topk_rules.h, walkfwd.h, cscv.h, tstats.h, costs.h, bootstrap.h, portfolio.h,
+// covariance.h), asks plan.h for its chunks and its staging layout, realises that layout in the engine's one arena
 // (engine_state.h), launches, and copies the results back before it returns. Nothing is computed on
 // the CPU but the walk-forward totals (walkfwd.cpp).
 #include <algorithm>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "bootstrap.h"
+#include "costs.h"
 #include "covariance.h"
 #include "cscv.h"
 #include "engine_state.h"
@@ -417,6 +418,58 @@ int32_t trade_stats_impl(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstat
     return 0;
 }
 
+// ---- bt_costs: every lane, or chosen lanes, under a ladder of fee levels (k_costs.hip)
+// The chunks of bt_trade_stats with C records per lane (CostsPlan); the level table goes to the
+// walk by value.
+int32_t costs_impl(bt_engine* e, int32_t C, const int32_t* levels, int32_t n, const bt_lane* lanes, bt_cost_rec* out,
+                   bt_cost_agg* agg) {
+    const char* fn = "bt_costs";
+    if (!e) refuse(fn, "null engine");
+    std::string why = costs_refusal(!e->syms.empty(), C, levels, n, lanes != nullptr, out != nullptr, agg != nullptr);
+    if (!why.empty()) refuse(fn, why);
+    const bool list = lanes != nullptr;
+    if (list && n == 0) return 0;
+    const int32_t S = (int32_t)e->syms.size(), P = e->P;
+    int32_t W = 0;
+    const std::vector<LaneRef> req = list ? resolve(e, fn, n, lanes, W) : std::vector<LaneRef>{};
+    const CostsPlan pl = plan_costs(list ? n : S, P, C, list, e->cus, e->costs_budget);
+    if (pl.per_chunk < 1)   // list mode: the records of one lane
+        refuse(fn, costs_budget_refusal(list ? 1 : P, C, e->costs_budget > 0 ? e->costs_budget : (int64_t)kCostsBudget));
+    uint8_t* base = enter(e, pl.staging_bytes);
+    CostLevels lv{};
+    for (int32_t j = 0; j < C; ++j) lv.fixed[j] = levels[2 * j], lv.bps[j] = levels[2 * j + 1];
+    CostArgs a{};
+    a.rec = at<bt_cost_rec>(base, pl.o_rec);
+    a.agg = agg ? at<bt_cost_agg>(base, pl.o_agg) : nullptr;
+    a.P = P;
+    a.C = C;
+    LaneRef* d_lanes = list ? at<LaneRef>(base, pl.o_lanes) : nullptr;
+    const size_t PC = (size_t)P * (size_t)C;
+    if (agg) HIPCHK(hipMemsetAsync(a.agg, 0, PC * sizeof(bt_cost_agg), main_stream(e)));
+    const size_t unit_recs = list ? (size_t)C : PC;
+    for_chunks(list ? (size_t)n : (size_t)S, (size_t)pl.per_chunk, [&](size_t i0, size_t m) {
+        if (list) {
+            HIPCHK(hipMemcpyAsync(d_lanes, req.data() + i0, m * sizeof(LaneRef), hipMemcpyHostToDevice, main_stream(e)));
+            a.lanes = d_lanes;
+            a.n = (int32_t)m;
+        } else {
+            a.syms = e->d_syms.p + i0;
+            a.n_rows = (int32_t)m;
+        }
+        HIPCHK(launch_cost_walk(a, lv, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, main_stream(e)));
+        if (agg) HIPCHK(launch_cost_agg(a, pl, main_stream(e)));
+        if (out)
+            HIPCHK(hipMemcpyAsync(out + i0 * unit_recs, a.rec, m * unit_recs * sizeof(bt_cost_rec), hipMemcpyDeviceToHost,
+                                  main_stream(e)));
+        HIPCHK(hipStreamSynchronize(main_stream(e)));
+    });
+    if (agg) {
+        HIPCHK(hipMemcpyAsync(agg, a.agg, PC * sizeof(bt_cost_agg), hipMemcpyDeviceToHost, main_stream(e)));
+        HIPCHK(hipStreamSynchronize(main_stream(e)));
+    }
+    return 0;
+}
+
 // ---- bt_bootstrap / bt_bootstrap_of: the bootstrap reality check (k_boot.hip)
 // The start table and vmax are made once; the lanes go through the lane kernel in the chunks of the
 // BootPlan (one chunk unless the prefix rows live in the arena or increments are staged); the
@@ -728,6 +781,15 @@ int32_t bt_trade_stats(bt_engine* e, int32_t n, const bt_lane* lanes, bt_tstats*
 
 int32_t bt_set_tstats_budget(bt_engine* e, int64_t bytes) {
     ABI_GUARD(-1, { return set_knob(e, "bt_set_tstats_budget", "bytes", bytes, -1, &EngineState::tstats_budget); })
+}
+
+int32_t bt_costs(bt_engine* e, int32_t C, const int32_t* levels, int32_t n, const bt_lane* lanes, bt_cost_rec* out,
+                 bt_cost_agg* agg) {
+    ABI_GUARD(-1, { return costs_impl(e, C, levels, n, lanes, out, agg); })
+}
+
+int32_t bt_set_costs_budget(bt_engine* e, int64_t bytes) {
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_costs_budget", "bytes", bytes, -1, &EngineState::costs_budget); })
 }
 
 int32_t bt_bootstrap(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t G, const int32_t* goff, int32_t from_bar,

@@ -113,6 +113,7 @@ struct EngineState {
     int64_t walkfwd_budget = 0;    // bt_set_walkfwd_budget (0 = kWalkfwdBudget)
     int64_t cscv_work = 0;         // bt_set_cscv_work (0 = kCscvWork)
     int64_t tstats_budget = 0;     // bt_set_tstats_budget (0 = kTstatsBudget)
+    int64_t costs_budget = 0;      // bt_set_costs_budget (0 = kCostsBudget)
     int64_t boot_budget = 0;       // bt_set_boot_budget (0 = kBootBudget)
     int32_t boot_row = 0;          // bt_set_boot_row (0 = the planner's choice, 1 = LDS, 2 = arena)
     int32_t portfolio_replicas = 0;  // bt_set_portfolio_replicas (0 = the planner's choice)

@@ -237,6 +237,27 @@ hipError_t launch_tstats_walk(const TsArgs& a, const int32_t* high, const int32_
                               const Grid& g, hipStream_t st);
 hipError_t launch_tstats_agg(const TsArgs& a, const TstatsPlan& pl, hipStream_t st);
 
+// Net of costs (k_costs.hip, bt_costs; docs/costs_spec.md) of one chunk. The walk (one wave64
+// workgroup per lane) leaves C bt_cost_rec per lane, levels innermost: with `lanes` the n staged
+// requests in order, else lane row * P + param of the chunk's n_rows dataset rows. The reduction
+// adds a chunk's [n_rows][P][C] records into agg[P][C], which the host zeroes before the first
+// chunk. The level table travels by value beside the arguments: one address for the whole grid,
+// read by scalar loads.
+struct CostArgs {
+    const SymDesc* syms;           // the chunk's rows (all-lanes mode)
+    const LaneRef* lanes;          // the chunk's requests (list mode), else nullptr
+    bt_cost_rec* rec;              // [n][C] or [n_rows][P][C]
+    bt_cost_agg* agg;              // [P][C] (reduction only)
+    int32_t n, n_rows, P, C;
+};
+struct CostLevels {
+    int32_t fixed[BT_COST_LEVELS_MAX], bps[BT_COST_LEVELS_MAX];
+};
+struct CostsPlan;
+hipError_t launch_cost_walk(const CostArgs& a, const CostLevels& lv, const int32_t* high, const int32_t* low,
+                            const int32_t* close, const Grid& g, hipStream_t st);
+hipError_t launch_cost_agg(const CostArgs& a, const CostsPlan& pl, hipStream_t st);
+
 // Bootstrap reality check (k_boot.hip, bt_bootstrap / bt_bootstrap_of; docs/bootstrap_spec.md).
 // The start kernel fills the start table and sets vmax to INT64_MIN once per call; the lane kernel
 // (one workgroup per lane of a chunk: lane lane0 + blockIdx.x of the call) builds the lane's prefix

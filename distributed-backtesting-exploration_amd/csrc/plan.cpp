@@ -569,6 +569,41 @@ TstatsPlan plan_tstats(int32_t units, int32_t P, bool list, int cus, int64_t bud
     return pl;
 }
 
+// ------------------------------------------------------------------------------ net of costs
+CostsPlan plan_costs(int32_t units, int32_t P, int32_t C, bool list, int cus, int64_t budget_req) {
+    constexpr int64_t kMaxGrid = 1LL << 30;   // one grid index per lane of a chunk
+    CostsPlan pl{};
+    units = std::max(units, 0);
+    P = std::max(P, 1);
+    C = std::min(std::max(C, 1), (int32_t)BT_COST_LEVELS_MAX);
+    pl.list = list;
+    pl.C = C;
+    const size_t budget = budget_req > 0 ? (size_t)budget_req : kCostsBudget;
+    const size_t lane_bytes = (size_t)C * sizeof(bt_cost_rec);
+    const int64_t PC = (int64_t)P * C;
+    pl.unit_bytes = list ? sizeof(LaneRef) + lane_bytes : (size_t)P * lane_bytes;
+    Carve c;
+    if (list) pl.o_lanes = c.take(0);
+    else pl.o_agg = c.take((size_t)PC * sizeof(bt_cost_agg));
+    // the chunk's regions each round up by less than kStagingAlign
+    const size_t fixed = c.end + (list ? 2 : 1) * kStagingAlign;
+    int64_t per = budget > fixed ? (int64_t)((budget - fixed) / pl.unit_bytes) : 0;
+    per = std::min<int64_t>(per, list ? kMaxGrid : kMaxGrid / P);
+    per = std::min<int64_t>(per, units);
+    pl.per_chunk = (int32_t)per;
+    pl.chunks = per > 0 ? (int32_t)((units + per - 1) / per) : 0;
+    pl.waves = list ? per : per * P;
+    pl.fill = (double)pl.waves / ((double)std::max(cus, 1) * 4 * 8);
+    pl.agg_block = (int32_t)(64 * std::min<int64_t>((PC + 63) / 64, 4));
+    pl.agg_pblocks = (int32_t)((PC + pl.agg_block - 1) / pl.agg_block);
+    pl.agg_slices = (int32_t)std::min<int64_t>(std::max<int64_t>((per + kCostsSliceRows - 1) / kCostsSliceRows, 1),
+                                               kCostsMaxSlices);
+    if (list) c.take((size_t)per * sizeof(LaneRef));
+    pl.o_rec = c.take((size_t)per * (list ? 1 : (size_t)P) * lane_bytes);
+    pl.staging_bytes = per > 0 ? fixed + (size_t)per * pl.unit_bytes : 0;
+    return pl;
+}
+
 // ------------------------------------------------------------------- bootstrap reality check
 BootPlan plan_boot(int64_t n, int64_t G, int32_t T, int32_t B, int32_t L, bool list, bool staged, bool want_boot,
                    int cus, int32_t row_req, int64_t budget_req) {

@@ -196,6 +196,31 @@ struct TstatsPlan {
 // `units`: S in all-lanes mode, n in list mode; `budget_req`: bt_set_tstats_budget (0 = kTstatsBudget).
 TstatsPlan plan_tstats(int32_t units, int32_t P, bool list, int cus, int64_t budget_req = 0);
 
+// What the net-of-costs call (k_costs.hip, bt_costs) is launched with: plan_tstats' chunks with C
+// records per lane. The units of a call are dataset rows of P lanes (all-lanes mode) or requested
+// lanes (list mode), processed in chunks of per_chunk (the last one shorter), every unit exactly
+// once; a chunk's device staging never exceeds the budget. All-lanes mode: agg[P * C], which the
+// reduction accumulates across the chunks, then the chunk's records [rows][P][C]. List mode: the
+// chunk's LaneRef, then its records [lanes][C]. per_chunk == 0: one unit alone does not fit, and
+// the call is refused. The reduction runs threads along q = p * C + j in blocks of agg_block,
+// agg_pblocks of them, and cuts a chunk's rows into at most kCostsMaxSlices slices of at least
+// kCostsSliceRows rows (grid y), each adding its part into agg with integer atomics.
+constexpr size_t kCostsBudget = 256u << 20;
+constexpr int32_t kCostsSliceRows = 64, kCostsMaxSlices = 64;
+struct CostsPlan {
+    bool list;
+    int32_t C;
+    int32_t per_chunk, chunks;
+    int64_t waves;                 // walk workgroups (one wave each) of a full chunk
+    double fill;                   // ... in units of what the device holds at once (8 waves per SIMD)
+    int32_t agg_block, agg_pblocks, agg_slices;
+    size_t unit_bytes;             // staging per row (P * C records) or per lane (LaneRef and C records)
+    size_t o_agg, o_lanes, o_rec;  // o_agg: all-lanes mode; o_lanes: list mode
+    size_t staging_bytes;          // of a full chunk (0 with per_chunk == 0)
+};
+// `units`: S in all-lanes mode, n in list mode; `budget_req`: bt_set_costs_budget (0 = kCostsBudget).
+CostsPlan plan_costs(int32_t units, int32_t P, int32_t C, bool list, int cus, int64_t budget_req = 0);
+
 // What a bootstrap reality check (k_boot.hip, bt_bootstrap / bt_bootstrap_of) of n lanes in G
 // groups over T bars, B resamples in blocks of L bars, is launched with. Blocks: Lp = min(L, T),
 // K = ceil(T / Lp) per resample, the last one of last_len bars. A lane's prefix row of T + 1 words

@@ -1198,6 +1198,26 @@ class Engine:
         identical whatever the budget."""
         _check(sym("bt_set_tstats_budget")(self._h, nbytes))
 
+    # ---- net of costs (costs.py, k_costs.hip)
+    def costs(self, levels, lanes=None, per_lane: bool = True, params: bool = False):
+        """Every lane of the resident dataset under a ladder of fee levels (docs/costs_spec.md):
+        `levels` is a sequence of at most 16 (fixed_ticks, bps) pairs, a fill at price px paying
+        fixed_ticks + floor(px * bps / 10000). Per (lane, level): the net pnl, the fees, the net
+        drawdown and where it bottoms, the bars under water, the sum of squared net increments and
+        which trades still win. With `lanes` (what replay takes) the records of those lanes in
+        request order, [n, C]; without, every lane as [S, P, C] (per_lane) and / or one aggregate
+        per (parameter, level) over every symbol, [P, C] (params). With per_lane=False nothing of
+        size S x P leaves the device. run() need not have been called. The call, its records and
+        its result type live in costs.py."""
+        from .costs import engine_costs
+        return engine_costs(self, levels, lanes, per_lane, params)
+
+    def set_costs_budget(self, nbytes: int) -> None:
+        """Device staging budget of costs in bytes: 0 = the default (256 MB). Results are identical
+        whatever the budget."""
+        from .costs import engine_set_costs_budget
+        engine_set_costs_budget(self, nbytes)
+
     # ---- bootstrap reality check (bt_bootstrap / bt_bootstrap_of, k_boot.hip)
     def reality_check(self, lanes=None, groups=None, resamples: int = 1000, block: int = 10, seed: int = 0,
                       window=None, per_lane: bool = False, vmax: bool = False, boot: bool = False) -> RealityCheck:

@@ -487,6 +487,56 @@ int32_t bt_trade_stats_host(int32_t n_trades, const bt_trade* trades, int32_t n_
                             const int64_t* equity, bt_tstats* out);
 int32_t bt_tstats_agg_host(int32_t S, int32_t P, const bt_tstats* recs, bt_tstats_agg* agg);
 int32_t bt_tstats_merge(const bt_tstats_agg* in, int32_t world, int32_t P, bt_tstats_agg* out);
+/* ---- net of costs: every lane under a ladder of fee levels (k_costs.hip, costs.cpp; semantics:
+ * docs/costs_spec.md). A call takes C in [1, BT_COST_LEVELS_MAX] levels, levels[2 j] = fixed_j in
+ * [0, BT_COST_FIXED_MAX] ticks per fill and levels[2 j + 1] = bps_j in [0, BT_COST_BPS_MAX]; a fill
+ * at price px pays fee_j(px) = fixed_j + floor(px * bps_j / 10000). Every trade of spec §4 has two
+ * fills, its entry at entry_bar at entry_px and its exit at exit_bar at exit_px (a flip puts both on
+ * one bar, a stop or target exit pays on the level price, the forced exit at B - 1 is a fill). With
+ * f_t the fees of bar t's fills the net curve is N_t = E_t - sum of f_u over u <= t, and a trade's
+ * net result is side (exit_px - entry_px) - fee_j(entry_px) - fee_j(exit_px). One bt_cost_rec per
+ * (lane, level), levels innermost; every figure is an exact integer and level j's record depends on
+ * level j alone.
+ *   list mode (lanes != NULL): the n lanes in request order, repeats allowed. out[n * C] is
+ *     required, agg must be NULL; n == 0 returns 0.
+ *   all-lanes mode (lanes == NULL, n == 0): out is [S * P * C] or NULL, agg is [P * C] (one
+ *     bt_cost_agg per (parameter, level) over every dataset row) or NULL, not both NULL. With out ==
+ *     NULL nothing of size S x P leaves the device.
+ * Synchronous like bt_trade_stats, and staged in chunks under a 256 MB budget in the same way.
+ * Added within ABI 3 (additive). Returns 0, or -1 with bt_last_error naming the offending value
+ * (the engine stays usable), checked in this order: a null engine, no dataset, C outside its range,
+ * levels == NULL, a level outside its ranges (the level is named), n < 0 or n > BT_COSTS_MAX, n != 0
+ * with lanes == NULL, agg given in list mode, out missing in list mode, both outputs NULL, an
+ * unknown symbol id, param outside [0, P), a budget smaller than one row's P * C records. */
+typedef struct bt_cost_rec {          /* 88 bytes */
+    int32_t n_trades, n_win, n_loss, n_bars;        /* trades; those with net > 0; with net < 0; B */
+    int32_t mdd_bar, underwater_bars;               /* first bar at the net mdd (-1 when it is 0); bars with N_t < peak_t */
+    int64_t pnl, fees, turnover;                    /* N_(B-1); sum of f_t; sum of the fill prices */
+    int64_t mdd;                                    /* max over t of peak_t - N_t, peak_t = max(0, N_0..N_t) */
+    int64_t win_sum, loss_sum;                      /* sum of net_i over wins; of -net_i over losses */
+    uint64_t s2_lo; int64_t s2_hi;                  /* sum over t of (N_t - N_(t-1))^2, an int128 as in bt_sums */
+} bt_cost_rec;
+typedef struct bt_cost_agg {          /* 48 bytes: one (parameter, level) over every dataset row */
+    int32_t n_sym, n_traded, n_profit, pad;         /* rows; rows with n_trades > 0; rows with pnl > 0; 0 */
+    int64_t trades, pnl, fees, mdd_max;             /* sums over the rows; the largest mdd */
+} bt_cost_agg;
+#define BT_COSTS_MAX (1 << 20)        /* lanes per call in list mode */
+#define BT_COST_LEVELS_MAX 16
+#define BT_COST_FIXED_MAX (1 << 20)
+#define BT_COST_BPS_MAX 1000
+int32_t bt_costs(bt_engine* e, int32_t C, const int32_t* levels, int32_t n, const bt_lane* lanes,
+                 bt_cost_rec* out, bt_cost_agg* agg);
+/* Device staging budget of bt_costs in bytes: 0 = the default (256 MB). Results are identical
+ * whatever the budget. */
+int32_t bt_set_costs_budget(bt_engine* e, int64_t bytes);
+/* Host, no GPU needed: the scalar restatements. One lane's C records from its complete trade list
+ * and its gross equity curve (n_bars values, as bt_replay returns them); the reduction of an
+ * S x P x C record array (row-major) to agg[P * C]; and the merge of `world` aggregates of PC
+ * records each (in[w * PC + q], disjoint row sets; world >= 1) into out[PC]. */
+int32_t bt_costs_host(int32_t n_trades, const bt_trade* trades, int32_t n_bars, const int64_t* equity,
+                      int32_t C, const int32_t* levels, bt_cost_rec* out);
+int32_t bt_costs_agg_host(int32_t S, int32_t P, int32_t C, const bt_cost_rec* recs, bt_cost_agg* agg);
+int32_t bt_costs_merge(const bt_cost_agg* in, int32_t world, int32_t PC, bt_cost_agg* out);
 /* ---- bootstrap reality check (k_boot.hip, bootstrap.cpp; semantics: docs/bootstrap_spec.md).
  * Is the best lane of a group luck? n lanes in G groups (group g holds lanes goff[g] .. goff[g+1] - 1)
  * over one window [from_bar, to_bar) of T = to_bar - from_bar bars (to_bar is NOT clipped to a row's
