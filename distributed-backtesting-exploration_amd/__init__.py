@@ -20,6 +20,8 @@ from .engine import (ABI_VERSION, FOLD_DTYPE, PIPE_SLOTS, WALKFWD_FOLDS_MAX, WF_
 from .overfit import CSCV_GROUP_DTYPE, CSCV_PICK_DTYPE, CSCV_RECORDS, Overfit, cscv_combos, cscv_host
 from .costs import (COST_AGG_DTYPE, COST_BPS_MAX, COST_DTYPE, COST_FIXED_MAX, COST_LEVELS_MAX, COST_RECORDS, COSTS_MAX,
                     Costs, costs_agg_host, costs_host, merge_costs)
+from .tail import (TAIL_ALL, TAIL_BARS_MAX, TAIL_DTYPE, TAIL_HELD, TAIL_LEVELS_MAX, TAIL_MAX, TAIL_PPM_MAX, TAIL_Q_DTYPE,
+                   TAIL_RECORDS, TailRisk, tail_risk_host)
 
 __all__ = [
     "ABI_VERSION", "FOLD_DTYPE", "PIPE_SLOTS", "WALKFWD_FOLDS_MAX", "WF_STEP_DTYPE", "WalkForward", "walk_forward_host", "BT_BOLL", "BT_DAILY", "BT_EMA_OLS", "BT_FLAG_PARITY", "BT_FLAG_TIMING", "BT_MINUTE",
@@ -34,4 +36,6 @@ __all__ = [
     "CSCV_PICK_DTYPE", "CSCV_PICKS_MAX", "CSCV_RECORDS", "Overfit", "cscv_combos", "cscv_host",
     "COST_AGG_DTYPE", "COST_BPS_MAX", "COST_DTYPE", "COST_FIXED_MAX", "COST_LEVELS_MAX", "COST_RECORDS", "COSTS_MAX",
     "Costs", "costs_agg_host", "costs_host", "merge_costs",
+    "TAIL_ALL", "TAIL_BARS_MAX", "TAIL_DTYPE", "TAIL_HELD", "TAIL_LEVELS_MAX", "TAIL_MAX", "TAIL_PPM_MAX", "TAIL_Q_DTYPE",
+    "TAIL_RECORDS", "TailRisk", "tail_risk_host",
 ]

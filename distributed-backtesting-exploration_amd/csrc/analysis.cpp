@@ -1,9 +1,10 @@
 // analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface, bt_surface_of, bt_topk_of,
-// bt_walk_forward, bt_cscv, bt_cscv_of, bt_trade_stats, bt_costs, bt_bootstrap, bt_bootstrap_of,
-// bt_portfolio, bt_covariance and bt_gram_of, with their settings (bt_set_*). This is the list the
-// other files point to. Each call checks its arguments with the pure rules of its header (replay.h,
-// surface.h, topk_rules.h, walkfwd.h, cscv.h, tstats.h, costs.h, bootstrap.h, portfolio.h,
-// covariance.h), asks plan.h for its chunks and its staging layout, realises that layout in the engine's one arena
+// bt_walk_forward, bt_cscv, bt_cscv_of, bt_trade_stats, bt_costs, bt_tail, bt_tail_of, bt_bootstrap,
+// bt_bootstrap_of, bt_portfolio, bt_covariance and bt_gram_of, with their settings (bt_set_*). This
+// is the list the other files point to. Each call checks its arguments with the pure rules of its
+// header (replay.h, surface.h, topk_rules.h, walkfwd.h, cscv.h, tstats.h, costs.h, tail.h,
+// bootstrap.h, portfolio.h, covariance.h), asks plan.h for its chunks and its staging layout,
+// realises that layout in the engine's one arena
 // (engine_state.h), launches, and copies the results back before it returns. Nothing is computed on
 // the CPU but the walk-forward totals (walkfwd.cpp).
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include "portfolio.h"
 #include "replay.h"
 #include "surface.h"
+#include "tail.h"
 #include "topk_rules.h"
 #include "tstats.h"
 #include "walkfwd.h"
@@ -470,6 +472,90 @@ int32_t costs_impl(bt_engine* e, int32_t C, const int32_t* levels, int32_t n, co
     return 0;
 }
 
+// ---- bt_tail / bt_tail_of: per-lane moments and lower-tail order statistics (k_tail.hip)
+// `req`: the resolved lanes of a list call; `d`: the increments of a staged call (rows of T); neither:
+// every lane of the dataset, `units` rows of P. `longest_n`: the most bars a lane can count. The
+// levels go up once; every chunk uploads its requests or its rows, runs one workgroup per lane and
+// brings its records back.
+int32_t tail_run(bt_engine* e, const char* fn, int32_t units, const std::vector<LaneRef>* req, const int32_t* d,
+                 int32_t longest_n, int32_t from, int32_t to, int32_t mode, int32_t Q, const int32_t* alpha_ppm,
+                 bt_tail_rec* recs, bt_tail_q* q) {
+    const bool list = req != nullptr, staged = d != nullptr;
+    const size_t P = list || staged ? 1 : (size_t)e->P;
+    const TailPlan pl = plan_tail(units, (int32_t)P, Q, list, staged, longest_n, e->cus, e->tail_row, e->tail_budget);
+    if (pl.row_refused) refuse(fn, tail_row_refusal(longest_n, (size_t)longest_n * 4, (size_t)pl.lds_row_cap * 4));
+    if (pl.per_chunk < 1)
+        refuse(fn, tail_budget_refusal(!list && !staged, pl.need_bytes, e->tail_budget > 0 ? (size_t)e->tail_budget : kTailBudget));
+    uint8_t* base = enter(e, pl.staging_bytes);
+    hipStream_t st = main_stream(e);
+    e->last_tail_row = pl.row_mode;
+    TailArgs a{};
+    a.levels = at<const int32_t>(base, pl.o_levels);
+    a.rec = recs ? at<bt_tail_rec>(base, pl.o_rec) : nullptr;
+    a.q = q ? at<bt_tail_q>(base, pl.o_q) : nullptr;
+    a.rows = pl.pitch > 0 ? at<int32_t>(base, pl.o_rows) : nullptr;
+    a.pitch = pl.pitch;
+    a.P = (int32_t)P, a.Q = Q;
+    a.from = from, a.to = to, a.held = mode == BT_TAIL_HELD ? 1 : 0;
+    a.T = staged ? longest_n : 0;
+    a.cap = longest_n;
+    LaneRef* d_lanes = list ? at<LaneRef>(base, pl.o_lanes) : nullptr;
+    HIPCHK(hipMemcpyAsync(base + pl.o_levels, alpha_ppm, (size_t)Q * 4, hipMemcpyHostToDevice, st));
+    for_chunks((size_t)units, (size_t)pl.per_chunk, [&](size_t i0, size_t m) {
+        const size_t lanes = m * P;
+        if (list) {
+            HIPCHK(hipMemcpyAsync(d_lanes, req->data() + i0, m * sizeof(LaneRef), hipMemcpyHostToDevice, st));
+            a.lanes = d_lanes;
+        } else if (staged) {
+            const size_t T = (size_t)longest_n;
+            HIPCHK(hipMemcpy2DAsync(a.rows, (size_t)pl.pitch * 4, d + i0 * T, T * 4, T * 4, m, hipMemcpyHostToDevice, st));
+        } else {
+            a.syms = e->d_syms.p + i0;
+        }
+        if (staged) HIPCHK(launch_tail_of(a, (int32_t)lanes, pl, st));
+        else HIPCHK(launch_tail_walk(a, (int32_t)lanes, pl, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, st));
+        if (recs)
+            HIPCHK(hipMemcpyAsync(recs + i0 * P, a.rec, lanes * sizeof(bt_tail_rec), hipMemcpyDeviceToHost, st));
+        if (q)
+            HIPCHK(hipMemcpyAsync(q + i0 * P * (size_t)Q, a.q, lanes * (size_t)Q * sizeof(bt_tail_q), hipMemcpyDeviceToHost,
+                                  st));
+        HIPCHK(hipStreamSynchronize(st));
+    });
+    return 0;
+}
+
+int32_t tail_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar, int32_t mode, int32_t Q,
+                  const int32_t* alpha_ppm, bt_tail_rec* recs, bt_tail_q* q) {
+    const char* fn = "bt_tail";
+    if (!e) refuse(fn, "null engine");
+    const std::string why = tail_refusal(!e->syms.empty(), n, lanes != nullptr, from_bar, to_bar, mode, Q, alpha_ppm,
+                                         recs != nullptr, q != nullptr, e->max_bars);
+    if (!why.empty()) refuse(fn, why);
+    const int32_t to = from_bar == 0 && to_bar == 0 ? INT32_MAX : to_bar;
+    if (lanes) {
+        int32_t W = 0;
+        const std::vector<LaneRef> req = resolve(e, fn, n, lanes, W);
+        return tail_run(e, fn, n, &req, nullptr, tail_longest(from_bar, to_bar, W), from_bar, to, mode, Q, alpha_ppm, recs, q);
+    }
+    return tail_run(e, fn, (int32_t)e->syms.size(), nullptr, nullptr, tail_longest(from_bar, to_bar, e->max_bars), from_bar,
+                    to, mode, Q, alpha_ppm, recs, q);
+}
+
+int32_t tail_of_impl(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t Q, const int32_t* alpha_ppm,
+                     bt_tail_rec* recs, bt_tail_q* q) {
+    const char* fn = "bt_tail_of";
+    if (!e) refuse(fn, "null engine");
+    std::string why = tail_of_refusal(n, T, d != nullptr, Q, alpha_ppm, recs != nullptr, q != nullptr);
+    if (why.empty()) why = increments_domain_refusal(n, T, d);
+    if (!why.empty()) refuse(fn, why);
+    return tail_run(e, fn, n, nullptr, d, T, 0, T, BT_TAIL_ALL, Q, alpha_ppm, recs, q);
+}
+
+int32_t last_tail_row_impl(bt_engine* e) {
+    if (!e) refuse("bt_last_tail_row", "null engine");
+    return e->last_tail_row;
+}
+
 // ---- bt_bootstrap / bt_bootstrap_of: the bootstrap reality check (k_boot.hip)
 // The start table and vmax are made once; the lanes go through the lane kernel in the chunks of the
 // BootPlan (one chunk unless the prefix rows live in the arena or increments are staged); the
@@ -790,6 +876,28 @@ int32_t bt_costs(bt_engine* e, int32_t C, const int32_t* levels, int32_t n, cons
 
 int32_t bt_set_costs_budget(bt_engine* e, int64_t bytes) {
     ABI_GUARD(-1, { return set_knob(e, "bt_set_costs_budget", "bytes", bytes, -1, &EngineState::costs_budget); })
+}
+
+int32_t bt_tail(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar, int32_t mode, int32_t Q,
+                const int32_t* alpha_ppm, bt_tail_rec* recs_out, bt_tail_q* q_out) {
+    ABI_GUARD(-1, { return tail_impl(e, n, lanes, from_bar, to_bar, mode, Q, alpha_ppm, recs_out, q_out); })
+}
+
+int32_t bt_tail_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t Q, const int32_t* alpha_ppm,
+                   bt_tail_rec* recs_out, bt_tail_q* q_out) {
+    ABI_GUARD(-1, { return tail_of_impl(e, n, T, d, Q, alpha_ppm, recs_out, q_out); })
+}
+
+int32_t bt_set_tail_row(bt_engine* e, int32_t mode) {
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_tail_row", "mode", mode, 2, &EngineState::tail_row); })
+}
+
+int32_t bt_set_tail_budget(bt_engine* e, int64_t bytes) {
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_tail_budget", "bytes", bytes, -1, &EngineState::tail_budget); })
+}
+
+int32_t bt_last_tail_row(bt_engine* e) {
+    ABI_GUARD(-1, { return last_tail_row_impl(e); })
 }
 
 int32_t bt_bootstrap(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t G, const int32_t* goff, int32_t from_bar,

@@ -114,6 +114,9 @@ struct EngineState {
     int64_t cscv_work = 0;         // bt_set_cscv_work (0 = kCscvWork)
     int64_t tstats_budget = 0;     // bt_set_tstats_budget (0 = kTstatsBudget)
     int64_t costs_budget = 0;      // bt_set_costs_budget (0 = kCostsBudget)
+    int64_t tail_budget = 0;       // bt_set_tail_budget (0 = kTailBudget)
+    int32_t tail_row = 0;          // bt_set_tail_row (0 = the planner's choice, 1 = LDS, 2 = arena)
+    int32_t last_tail_row = 0;     // bt_last_tail_row: the home the last bt_tail / bt_tail_of used
     int64_t boot_budget = 0;       // bt_set_boot_budget (0 = kBootBudget)
     int32_t boot_row = 0;          // bt_set_boot_row (0 = the planner's choice, 1 = LDS, 2 = arena)
     int32_t portfolio_replicas = 0;  // bt_set_portfolio_replicas (0 = the planner's choice)

@@ -1,5 +1,5 @@
 // host_common.h — what the host rule files of the analysis calls (surface.cpp, walkfwd.cpp,
-// cscv.cpp, tstats.cpp, costs.cpp, bootstrap.cpp, portfolio.cpp, covariance.cpp) and analysis.cpp share: the
+// cscv.cpp, tstats.cpp, costs.cpp, tail.cpp, bootstrap.cpp, portfolio.cpp, covariance.cpp) and analysis.cpp share: the
 // one error path of a HIP-free entry point, the int128 word helpers, the host Sharpe of fold
 // sums and the rules of replayed curves and staged increments. No HIP include: a plain host compiler builds it (the drivers under
 // tests/asan); internal.h includes it, so the word helpers serve the kernels too.

@@ -258,6 +258,26 @@ hipError_t launch_cost_walk(const CostArgs& a, const CostLevels& lv, const int32
                             const int32_t* close, const Grid& g, hipStream_t st);
 hipError_t launch_cost_agg(const CostArgs& a, const CostsPlan& pl, hipStream_t st);
 
+// Tail risk (k_tail.hip, bt_tail / bt_tail_of; docs/tail_spec.md) of one chunk of m lanes, one
+// workgroup each: with `lanes` the chunk's staged requests, with `d` its staged rows of T increments
+// ([m][pitch]), else lane row * P + param of the chunk's dataset rows. rec and q may each be nullptr.
+struct TailArgs {
+    const SymDesc* syms;           // the chunk's rows (all-lanes mode)
+    const LaneRef* lanes;          // the chunk's requests (list mode), else nullptr
+    const int32_t* levels;         // [Q] alpha_ppm
+    bt_tail_rec* rec;              // [m] or nullptr
+    bt_tail_q* q;                  // [m][Q] or nullptr
+    int32_t* rows;                 // [m][pitch]: the arena rows, or the staged increments
+    int64_t pitch;
+    int32_t P, Q, from, to, held;  // the window [from, to) (to already resolved), BT_TAIL_HELD
+    int32_t T;                     // bars of a staged row
+    int32_t cap;                   // counted bars a lane's row holds (the plan's longest_n)
+};
+struct TailPlan;
+hipError_t launch_tail_walk(const TailArgs& a, int32_t m, const TailPlan& pl, const int32_t* high, const int32_t* low,
+                            const int32_t* close, const Grid& g, hipStream_t st);
+hipError_t launch_tail_of(const TailArgs& a, int32_t m, const TailPlan& pl, hipStream_t st);
+
 // Bootstrap reality check (k_boot.hip, bt_bootstrap / bt_bootstrap_of; docs/bootstrap_spec.md).
 // The start kernel fills the start table and sets vmax to INT64_MIN once per call; the lane kernel
 // (one workgroup per lane of a chunk: lane lane0 + blockIdx.x of the call) builds the lane's prefix

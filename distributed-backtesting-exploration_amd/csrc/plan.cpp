@@ -604,6 +604,46 @@ CostsPlan plan_costs(int32_t units, int32_t P, int32_t C, bool list, int cus, in
     return pl;
 }
 
+// --------------------------------------------------------------------------------- tail risk
+TailPlan plan_tail(int32_t units, int32_t P, int32_t Q, bool list, bool staged, int32_t longest_n, int cus,
+                   int32_t row_req, int64_t budget_req) {
+    (void)cus;                                     // one workgroup per lane whatever the device
+    constexpr int64_t kMaxGrid = 1LL << 30;        // one grid index per lane of a chunk
+    TailPlan pl{};
+    units = std::max(units, 0);
+    P = list || staged ? 1 : std::max(P, 1);
+    Q = std::min(std::max(Q, 1), (int32_t)BT_TAIL_LEVELS_MAX);
+    longest_n = std::max(longest_n, 0);
+    pl.list = list, pl.staged = staged, pl.Q = Q;
+    pl.lds_row_cap = (int32_t)((kTailLdsBytes - kTailFixedBytes) / 4);
+    const bool fits = longest_n <= pl.lds_row_cap;
+    pl.row_refused = row_req == 1 && !fits;
+    pl.row_mode = row_req == 2 || !fits ? 2 : 1;
+    pl.block = 64 * kTailWaves;
+    pl.lds_bytes = kTailFixedBytes + (pl.row_mode == 1 ? (size_t)longest_n * 4 : 0);
+    pl.pitch = pl.row_mode == 2 || staged ? std::max<int64_t>(((int64_t)longest_n + 63) / 64 * 64, 64) : 0;
+    const size_t budget = budget_req > 0 ? (size_t)budget_req : kTailBudget;
+    const size_t lane_bytes = sizeof(bt_tail_rec) + (size_t)Q * sizeof(bt_tail_q) + (size_t)pl.pitch * 4;
+    pl.unit_bytes = (size_t)P * lane_bytes + (list ? sizeof(LaneRef) : 0);
+    Carve c;
+    pl.o_levels = c.take((size_t)Q * 4);
+    // the chunk's four regions each round up by less than kStagingAlign
+    const size_t fixed = c.end + 4 * kStagingAlign;
+    pl.need_bytes = fixed + pl.unit_bytes;
+    int64_t per = budget > fixed ? (int64_t)((budget - fixed) / pl.unit_bytes) : 0;
+    per = std::min<int64_t>(per, kMaxGrid / P);
+    per = std::min<int64_t>(per, units);
+    pl.per_chunk = (int32_t)per;
+    pl.chunks = per > 0 ? (int32_t)((units + per - 1) / per) : 0;
+    const size_t lanes = (size_t)per * (size_t)P;
+    pl.o_lanes = c.take(list ? lanes * sizeof(LaneRef) : 0);
+    pl.o_rec = c.take(lanes * sizeof(bt_tail_rec));
+    pl.o_q = c.take(lanes * (size_t)Q * sizeof(bt_tail_q));
+    pl.o_rows = c.take(lanes * (size_t)pl.pitch * 4);
+    pl.staging_bytes = per > 0 ? c.staging_bytes() : 0;
+    return pl;
+}
+
 // ------------------------------------------------------------------- bootstrap reality check
 BootPlan plan_boot(int64_t n, int64_t G, int32_t T, int32_t B, int32_t L, bool list, bool staged, bool want_boot,
                    int cus, int32_t row_req, int64_t budget_req) {

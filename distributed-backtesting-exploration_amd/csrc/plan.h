@@ -221,6 +221,43 @@ struct CostsPlan {
 // `units`: S in all-lanes mode, n in list mode; `budget_req`: bt_set_costs_budget (0 = kCostsBudget).
 CostsPlan plan_costs(int32_t units, int32_t P, int32_t C, bool list, int cus, int64_t budget_req = 0);
 
+// What the tail-risk call (k_tail.hip, bt_tail / bt_tail_of) is launched with. The units of a call
+// are dataset rows of P lanes (all-lanes mode), requested lanes (list mode) or staged rows of
+// increments (bt_tail_of), processed in chunks of per_chunk, every unit exactly once; a chunk's
+// staging never exceeds the budget. One workgroup of `block` threads per lane: its first wave walks
+// (or reads the staged row) and leaves the counted increments as int32 in the lane's row, then the
+// whole workgroup selects on it. The row lives in dynamic LDS behind kTailFixedBytes of histograms
+// and scratch (row_mode 1) while longest_n, the most bars a lane can count, is at most lds_row_cap,
+// else in the arena (row_mode 2) in rows of `pitch` words, whole 256-byte lines. A staged call
+// uploads into the arena rows whatever the home and, with row_mode 1, copies them to LDS. Regions:
+// the levels [Q] int32, the chunk's LaneRef (list mode), its records, its quantile records [lanes][Q]
+// and its rows. row_refused: bt_set_tail_row(e, 1) with a row above lds_row_cap. per_chunk == 0: one
+// unit alone (need_bytes) does not fit the budget, and the call is refused.
+constexpr size_t kTailBudget = 256u << 20;
+constexpr size_t kTailLdsBytes = 64 * 1024;    // dynamic LDS of a workgroup: two workgroups per CU at least
+constexpr size_t kTailHistBytes = BT_TAIL_LEVELS_MAX * 256 * 4;   // one 256-bin histogram per level
+constexpr size_t kTailFixedBytes = kTailHistBytes + 1024;        // ... and the workgroup's scratch, in front of the row
+constexpr int32_t kTailWaves = 4;
+struct TailPlan {
+    bool list, staged;
+    int32_t Q;
+    int32_t row_mode;              // 1 = LDS, 2 = arena
+    bool row_refused;
+    int32_t lds_row_cap;           // counted bars an LDS row holds
+    int32_t block;
+    size_t lds_bytes;              // dynamic LDS of a workgroup
+    int64_t pitch;                 // words of an arena row (0: none)
+    int32_t per_chunk, chunks;
+    size_t unit_bytes, need_bytes; // staging per unit; of the fixed part and one unit
+    size_t o_levels, o_lanes, o_rec, o_q, o_rows;
+    size_t staging_bytes;          // of a full chunk (0 with per_chunk == 0)
+};
+// `units`: S in all-lanes mode, n in list mode and of a staged call; `longest_n`: the window clipped
+// to the longest row, or T of a staged call; `row_req`: bt_set_tail_row; `budget_req`:
+// bt_set_tail_budget (0 = kTailBudget).
+TailPlan plan_tail(int32_t units, int32_t P, int32_t Q, bool list, bool staged, int32_t longest_n, int cus,
+                   int32_t row_req = 0, int64_t budget_req = 0);
+
 // What a bootstrap reality check (k_boot.hip, bt_bootstrap / bt_bootstrap_of) of n lanes in G
 // groups over T bars, B resamples in blocks of L bars, is launched with. Blocks: Lp = min(L, T),
 // K = ceil(T / Lp) per resample, the last one of last_len bars. A lane's prefix row of T + 1 words

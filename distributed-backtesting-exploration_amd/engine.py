@@ -1218,6 +1218,43 @@ class Engine:
         from .costs import engine_set_costs_budget
         engine_set_costs_budget(self, nbytes)
 
+    # ---- tail risk (tail.py, k_tail.hip)
+    def tail_risk(self, levels=(0.01, 0.05), lanes=None, window=None, held: bool = False):
+        """The shape of every lane's per-bar pnl (docs/tail_spec.md): per lane the counts, the
+        extremes and where they fall, and the exact power sums up to the fourth of its increments
+        d_t over the window's bars (with `held` only the bars a position was held into), and per
+        (lane, level) the value at risk and the expected shortfall as exact order statistics.
+        `levels`: at most 8 lower-tail levels, fractions (0.05) or integer parts per million. With
+        `lanes` (what replay takes) the records of those lanes in request order, [n]; without,
+        every lane as [S, P]. run() need not have been called. The call, its records and its result
+        type (TailRisk, with the moments, ratios, psr and deflated_sharpe) live in tail.py."""
+        from .tail import engine_tail_risk
+        return engine_tail_risk(self, levels, lanes, window, held)
+
+    def tail_of(self, d, levels=(0.01, 0.05)):
+        """The tail kernels on a caller's increments: an [n, T] integer array with |d| < 2^31. Every
+        entry is counted. Needs no dataset."""
+        from .tail import engine_tail_of
+        return engine_tail_of(self, d, levels)
+
+    def set_tail_row(self, mode: int) -> None:
+        """Where tail_risk and tail_of keep a lane's row of counted increments: 0 = the planner's
+        choice, 1 = LDS (refused at call time when the row does not fit), 2 = device memory.
+        Results are identical under every setting."""
+        from .tail import engine_set_tail_row
+        engine_set_tail_row(self, mode)
+
+    def set_tail_budget(self, nbytes: int) -> None:
+        """Device staging budget of tail_risk and tail_of in bytes: 0 = the default (256 MB).
+        Results are identical whatever the budget."""
+        from .tail import engine_set_tail_budget
+        engine_set_tail_budget(self, nbytes)
+
+    def last_tail_row(self) -> int:
+        """The row home the last tail_risk / tail_of used: 1 = LDS, 2 = device memory, 0 = none yet."""
+        from .tail import engine_last_tail_row
+        return engine_last_tail_row(self)
+
     # ---- bootstrap reality check (bt_bootstrap / bt_bootstrap_of, k_boot.hip)
     def reality_check(self, lanes=None, groups=None, resamples: int = 1000, block: int = 10, seed: int = 0,
                       window=None, per_lane: bool = False, vmax: bool = False, boot: bool = False) -> RealityCheck:

@@ -537,6 +537,66 @@ int32_t bt_costs_host(int32_t n_trades, const bt_trade* trades, int32_t n_bars, 
                       int32_t C, const int32_t* levels, bt_cost_rec* out);
 int32_t bt_costs_agg_host(int32_t S, int32_t P, int32_t C, const bt_cost_rec* recs, bt_cost_agg* agg);
 int32_t bt_costs_merge(const bt_cost_agg* in, int32_t world, int32_t PC, bt_cost_agg* out);
+/* ---- tail risk: the shape of a lane's per-bar pnl (k_tail.hip, tail.cpp; semantics:
+ * docs/tail_spec.md). Every lane is walked once over its whole series; its increments are d_t = E_t -
+ * E_(t-1) with E_(-1) = 0, |d_t| < 2^31. The window is [from_bar, to_bar), from_bar = to_bar = 0
+ * meaning the whole row; lane i contributes the n_window bars from_bar <= t < min(to_bar, B_i) (there
+ * may be none). mode BT_TAIL_ALL counts every bar of the window, BT_TAIL_HELD only the bars a
+ * position was held into (t >= 1 and pos_(t-1) != 0; on the other bars d_t is 0). Over the n counted
+ * bars one bt_tail_rec per lane holds the counts, the extremes with the first bar that reaches each,
+ * and the exact power sums up to the fourth; per (lane, level), levels innermost, one bt_tail_q
+ * holds the lower-tail order statistics at alpha_ppm[j] in [1, 10^6] parts per million: with
+ * k = ceil(n * alpha_ppm / 10^6), var is the k-th smallest counted d, es_sum the sum of the k
+ * smallest and n_lt the number of counted d below var, so that es_sum = (sum of the d < var) +
+ * (k - n_lt) * var. Q in [1, BT_TAIL_LEVELS_MAX] levels, in any order, repeats allowed; a level's
+ * result depends on that level alone. With n = 0 both records are all zeros but min_bar = max_bar =
+ * -1. Every figure is an exact integer, whatever the chunking, the budget or the home of the row.
+ *   list mode (lanes != NULL): n in [1, BT_TAIL_MAX] lanes in request order, repeats allowed;
+ *     recs_out[n], q_out[n * Q].
+ *   all-lanes mode (lanes == NULL, n == 0): recs_out[S * P], q_out[S * P * Q].
+ * Either output may be NULL, not both. Synchronous; bt_run need not have been called. Added within
+ * ABI 3 (additive). Returns 0, or -1 with bt_last_error naming the offending value (the engine stays
+ * usable), checked in this order: a null engine, no dataset, n, Q, alpha_ppm == NULL, a level outside
+ * its range (the level is named), mode, the window, both outputs NULL, a dataset row longer than
+ * BT_TAIL_BARS_MAX, an unknown symbol id, param outside [0, P), a row that does not fit LDS under
+ * bt_set_tail_row(e, 1), a staging need above the budget (the bytes are named). */
+typedef struct bt_tail_rec {          /* 128 bytes */
+    int32_t n, n_window, n_pos, n_neg;              /* counted bars; bars of the window; counted d > 0; d < 0 */
+    int32_t min_bar, max_bar;                       /* the smallest t that reaches min_d / max_d (-1 when n = 0) */
+    int64_t min_d, max_d, s1, s1_neg;               /* extremes; sum of d; sum of min(d, 0) */
+    bt_wide s2, s2_neg, s3;                         /* sum of d^2; of min(d, 0)^2; of d^3 (signed) */
+    uint64_t s4[3];                                 /* sum of d^4, 192 bits, least significant word first */
+} bt_tail_rec;
+typedef struct bt_tail_q {            /* 24 bytes */
+    int64_t var, es_sum;                            /* the k-th smallest counted d; the sum of the k smallest */
+    int32_t k, n_lt;                                /* ceil(n alpha / 10^6); counted d < var */
+} bt_tail_q;
+enum bt_tail_mode { BT_TAIL_ALL = 0, BT_TAIL_HELD = 1 };
+#define BT_TAIL_MAX (1 << 20)         /* lanes per call in list mode, rows of bt_tail_of */
+#define BT_TAIL_LEVELS_MAX 8
+#define BT_TAIL_PPM_MAX 1000000
+#define BT_TAIL_BARS_MAX (1 << 22)    /* bars of a row */
+int32_t bt_tail(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar, int32_t mode,
+                int32_t Q, const int32_t* alpha_ppm, bt_tail_rec* recs_out, bt_tail_q* q_out);
+/* The same kernels on a caller's increments d[n][T] (row-major int32, |d| < 2^31: INT32_MIN is
+ * refused with its index), n in [1, BT_TAIL_MAX], T in [1, BT_TAIL_BARS_MAX]. Every entry is counted
+ * and min_bar / max_bar are indices into the row. Needs no dataset. */
+int32_t bt_tail_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t Q, const int32_t* alpha_ppm,
+                   bt_tail_rec* recs_out, bt_tail_q* q_out);
+/* Where a lane's row of counted increments lives during the selection: 0 = the planner's choice, 1 =
+ * LDS (a call whose longest row does not fit is refused), 2 = device memory. bt_set_tail_budget: the
+ * device staging budget in bytes, 0 = the default (256 MB). Results are identical under every
+ * setting. bt_last_tail_row: the home the last bt_tail / bt_tail_of of this engine used (1 or 2; 0
+ * before the first). */
+int32_t bt_set_tail_row(bt_engine* e, int32_t mode);
+int32_t bt_set_tail_budget(bt_engine* e, int64_t bytes);
+int32_t bt_last_tail_row(bt_engine* e);
+/* Host, no GPU needed: the scalar restatement from replayed curves, n lanes with equity rows of
+ * `stride` values, n_bars[i] of them meaningful, and the pos rows bt_replay returns (pos may be NULL
+ * with mode BT_TAIL_ALL only). It sorts a copy of every row. */
+int32_t bt_tail_host(int32_t n, const int64_t* equity, const int8_t* pos, const int32_t* n_bars, int64_t stride,
+                     int32_t from_bar, int32_t to_bar, int32_t mode, int32_t Q, const int32_t* alpha_ppm,
+                     bt_tail_rec* recs_out, bt_tail_q* q_out);
 /* ---- bootstrap reality check (k_boot.hip, bootstrap.cpp; semantics: docs/bootstrap_spec.md).
  * Is the best lane of a group luck? n lanes in G groups (group g holds lanes goff[g] .. goff[g+1] - 1)
  * over one window [from_bar, to_bar) of T = to_bar - from_bar bars (to_bar is NOT clipped to a row's
