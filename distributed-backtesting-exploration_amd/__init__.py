@@ -22,6 +22,7 @@ from .costs import (COST_AGG_DTYPE, COST_BPS_MAX, COST_DTYPE, COST_FIXED_MAX, CO
                     Costs, costs_agg_host, costs_host, merge_costs)
 from .tail import (TAIL_ALL, TAIL_BARS_MAX, TAIL_DTYPE, TAIL_HELD, TAIL_LEVELS_MAX, TAIL_MAX, TAIL_PPM_MAX, TAIL_Q_DTYPE,
                    TAIL_RECORDS, TailRisk, tail_risk_host)
+from .ddrisk import DD_LANE_DTYPE, DD_LEVELS_MAX, DD_LIMITS_MAX, DD_RECORDS, DrawdownRisk, drawdown_risk_host
 
 __all__ = [
     "ABI_VERSION", "FOLD_DTYPE", "PIPE_SLOTS", "WALKFWD_FOLDS_MAX", "WF_STEP_DTYPE", "WalkForward", "walk_forward_host", "BT_BOLL", "BT_DAILY", "BT_EMA_OLS", "BT_FLAG_PARITY", "BT_FLAG_TIMING", "BT_MINUTE",
@@ -38,4 +39,5 @@ __all__ = [
     "Costs", "costs_agg_host", "costs_host", "merge_costs",
     "TAIL_ALL", "TAIL_BARS_MAX", "TAIL_DTYPE", "TAIL_HELD", "TAIL_LEVELS_MAX", "TAIL_MAX", "TAIL_PPM_MAX", "TAIL_Q_DTYPE",
     "TAIL_RECORDS", "TailRisk", "tail_risk_host",
+    "DD_LANE_DTYPE", "DD_LEVELS_MAX", "DD_LIMITS_MAX", "DD_RECORDS", "DrawdownRisk", "drawdown_risk_host",
 ]

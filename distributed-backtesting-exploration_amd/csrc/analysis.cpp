@@ -1,9 +1,10 @@
 // analysis.cpp — the analysis calls of the C ABI: bt_replay, bt_surface, bt_surface_of, bt_topk_of,
 // bt_walk_forward, bt_cscv, bt_cscv_of, bt_trade_stats, bt_costs, bt_tail, bt_tail_of, bt_bootstrap,
-// bt_bootstrap_of, bt_portfolio, bt_covariance and bt_gram_of, with their settings (bt_set_*). This
+// bt_bootstrap_of, bt_drawdown_boot, bt_drawdown_boot_of, bt_portfolio, bt_covariance and bt_gram_of,
+// with their settings (bt_set_*). This
 // is the list the other files point to. Each call checks its arguments with the pure rules of its
 // header (replay.h, surface.h, topk_rules.h, walkfwd.h, cscv.h, tstats.h, costs.h, tail.h,
-// bootstrap.h, portfolio.h, covariance.h), asks plan.h for its chunks and its staging layout,
+// bootstrap.h, ddboot.h, portfolio.h, covariance.h), asks plan.h for its chunks and its staging layout,
 // realises that layout in the engine's one arena
 // (engine_state.h), launches, and copies the results back before it returns. Nothing is computed on
 // the CPU but the walk-forward totals (walkfwd.cpp).
@@ -16,6 +17,7 @@
 #include "costs.h"
 #include "covariance.h"
 #include "cscv.h"
+#include "ddboot.h"
 #include "engine_state.h"
 #include "portfolio.h"
 #include "replay.h"
@@ -668,6 +670,123 @@ int32_t bootstrap_of_impl(bt_engine* e, int32_t n, int32_t T, const int32_t* d, 
     return boot_run(e, fn, n, G, goff, nullptr, d, 0, T, B, L, seed, out);
 }
 
+// ---- bt_drawdown_boot / bt_drawdown_boot_of: the bootstrap of every lane's largest drawdown (k_ddboot.hip)
+// The start table (the reality check's kernel), the levels and the limits are made once; the lanes go
+// through the lane kernel in the chunks of the DdPlan, and every chunk brings its own results back.
+struct DdOut {
+    bt_dd_lane* rec;
+    int64_t* q;
+    int64_t* reach;
+    int64_t* raw;
+};
+
+// `req`: the resolved lanes of a list call; `d`: the increments of a staged call; neither: every
+// lane of the dataset.
+int32_t dd_run(bt_engine* e, const char* fn, int64_t n, const std::vector<LaneRef>* req, const int32_t* d, int32_t from,
+               int32_t T, int32_t B, int32_t L, uint64_t seed, int32_t Q, const int32_t* alpha_ppm, int32_t R,
+               const int64_t* limits, DdOut out) {
+    const bool list = req != nullptr, staged = d != nullptr;
+    if (Q == 0) out.q = nullptr;
+    if (R == 0) out.reach = nullptr;
+    if (!out.q) Q = 0;               // levels nobody reads are not selected
+    if (!out.reach) R = 0;
+    const DdPlan pl = plan_ddboot(n, T, B, L, Q, R, list, staged, out.raw != nullptr, e->cus, e->ddboot_row, e->ddboot_budget);
+    std::string why;
+    if (pl.row_refused) why = dd_row_refusal(T, pl.row_bytes, kDdLdsBytes - kDdFixedBytes);
+    if (why.empty()) why = dd_budget_refusal(pl.need_bytes, e->ddboot_budget > 0 ? (size_t)e->ddboot_budget : kDdBudget);
+    if (!why.empty()) refuse(fn, why);
+    uint8_t* base = enter(e, pl.staging_bytes);
+    hipStream_t st = main_stream(e);
+    e->last_ddboot_row = pl.row_mode;
+    DdArgs a{};
+    a.syms = e->d_syms.p;
+    a.lanes = list ? at<const LaneRef>(base, pl.o_lanes) : nullptr;
+    a.d = staged ? at<const int32_t>(base, pl.o_d) : nullptr;
+    a.starts = at<const int32_t>(base, pl.o_starts);
+    a.levels = at<const int32_t>(base, pl.o_levels);
+    a.limits = at<const int64_t>(base, pl.o_limits);
+    a.rows = pl.row_mode == 2 ? base + pl.o_rows : nullptr;
+    a.vals = pl.v_pitch > 0 ? at<int64_t>(base, pl.o_vals) : nullptr;
+    a.raw = out.raw ? at<int64_t>(base, pl.o_raw) : nullptr;
+    a.rec = out.rec ? at<bt_dd_lane>(base, pl.o_rec) : nullptr;
+    a.q = out.q ? at<int64_t>(base, pl.o_q) : nullptr;
+    a.reach = out.reach ? at<int64_t>(base, pl.o_reach) : nullptr;
+    a.pitch = pl.pitch, a.d_pitch = pl.d_pitch, a.v_pitch = pl.v_pitch;
+    a.r_w1 = (uint32_t)pl.r_w1, a.r_w2 = (uint32_t)pl.r_w2, a.l_vals = (uint32_t)pl.l_vals;
+    a.P = list || staged ? 1 : e->P;
+    a.from = from, a.T = T, a.B = B, a.Lp = pl.Lp, a.K = pl.K, a.last_len = pl.last_len, a.Q = Q, a.R = R;
+    if (Q > 0) HIPCHK(hipMemcpyAsync(base + pl.o_levels, alpha_ppm, (size_t)Q * 4, hipMemcpyHostToDevice, st));
+    if (R > 0) HIPCHK(hipMemcpyAsync(base + pl.o_limits, limits, (size_t)R * 8, hipMemcpyHostToDevice, st));
+    // the reality check's start kernel, with no group: it writes the table alone
+    BootArgs sa{};
+    sa.starts = a.starts;
+    sa.T = T, sa.B = B, sa.K = pl.K;
+    BootPlan sp{};
+    sp.starts_block = pl.starts_block, sp.starts_blocks = pl.starts_blocks;
+    HIPCHK(launch_boot_starts(sa, sp, seed, st));
+    HIPCHK(prepare_dd(pl, staged, e->grid));
+    for_chunks((size_t)n, (size_t)pl.per_chunk, [&](size_t i0, size_t m) {
+        a.lane0 = (int64_t)i0;
+        if (list) HIPCHK(hipMemcpyAsync(base + pl.o_lanes, req->data() + i0, m * sizeof(LaneRef), hipMemcpyHostToDevice, st));
+        if (staged) {
+            HIPCHK(hipMemcpy2DAsync(base + pl.o_d, (size_t)pl.d_pitch * 4, d + i0 * (size_t)T, (size_t)T * 4, (size_t)T * 4,
+                                    m, hipMemcpyHostToDevice, st));
+            HIPCHK(launch_dd_of(a, (int32_t)m, pl, st));
+        } else {
+            HIPCHK(launch_dd_walk(a, (int32_t)m, pl, e->d_h.p, e->d_l.p, e->d_c.p, e->grid, st));
+        }
+        if (out.rec) HIPCHK(hipMemcpyAsync(out.rec + i0, a.rec, m * sizeof(bt_dd_lane), hipMemcpyDeviceToHost, st));
+        if (out.q) HIPCHK(hipMemcpyAsync(out.q + i0 * (size_t)Q, a.q, m * (size_t)Q * 8, hipMemcpyDeviceToHost, st));
+        if (out.reach)
+            HIPCHK(hipMemcpyAsync(out.reach + i0 * (size_t)R, a.reach, m * (size_t)R * 8, hipMemcpyDeviceToHost, st));
+        if (out.raw) HIPCHK(hipMemcpyAsync(out.raw + i0 * (size_t)B, a.raw, m * (size_t)B * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    });
+    return 0;
+}
+
+int32_t drawdown_boot_impl(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar, int32_t B,
+                           int32_t L, uint64_t seed, int32_t Q, const int32_t* alpha_ppm, int32_t R, const int64_t* limits,
+                           const DdOut& out) {
+    const char* fn = "bt_drawdown_boot";
+    const DdCall call{e != nullptr, e && !e->syms.empty(), false, lanes != nullptr, n, from_bar, B, L, Q, alpha_ppm, R, limits,
+                      out.rec != nullptr, out.q != nullptr, out.reach != nullptr, out.raw != nullptr};
+    std::string why = dd_refusal(call);
+    if (!why.empty()) refuse(fn, why);
+    int32_t T = 0;
+    if (lanes) {
+        int32_t W = 0;
+        const std::vector<LaneRef> req = resolve(e, fn, n, lanes, W);
+        why = boot_window(from_bar, to_bar, W, T);
+        if (!why.empty()) refuse(fn, why);
+        return dd_run(e, fn, n, &req, nullptr, from_bar, T, B, L, seed, Q, alpha_ppm, R, limits, out);
+    }
+    why = boot_window(from_bar, to_bar, e->max_bars, T);
+    if (!why.empty()) refuse(fn, why);
+    return dd_run(e, fn, (int64_t)e->syms.size() * e->P, nullptr, nullptr, from_bar, T, B, L, seed, Q, alpha_ppm, R, limits,
+                  out);
+}
+
+int32_t drawdown_boot_of_impl(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t B, int32_t L, uint64_t seed,
+                              int32_t Q, const int32_t* alpha_ppm, int32_t R, const int64_t* limits, const DdOut& out) {
+    const char* fn = "bt_drawdown_boot_of";
+    const DdCall call{e != nullptr, false, true, d != nullptr, n, 0, B, L, Q, alpha_ppm, R, limits,
+                      out.rec != nullptr, out.q != nullptr, out.reach != nullptr, out.raw != nullptr};
+    // T before the rest: a row without bars has no d to ask for
+    int32_t Tw = 0;
+    std::string why = e ? boot_window(0, T, 0, Tw) : "";
+    if (why.empty()) why = dd_refusal(call);
+    if (!why.empty()) refuse(fn, why);
+    why = increments_domain_refusal(n, T, d);
+    if (!why.empty()) refuse(fn, why);
+    return dd_run(e, fn, n, nullptr, d, 0, T, B, L, seed, Q, alpha_ppm, R, limits, out);
+}
+
+int32_t last_ddboot_row_impl(bt_engine* e) {
+    if (!e) refuse("bt_last_ddboot_row", "null engine");
+    return e->last_ddboot_row;
+}
+
 // ---- bt_portfolio: chosen lanes traded together, per bar (k_portfolio.hip)
 // The entries with a non-empty window go up once, the accumulators are zeroed, the walk adds into
 // them and the finish writes the four rows and the summary, which one copy brings back.
@@ -923,6 +1042,36 @@ int32_t bt_set_boot_budget(bt_engine* e, int64_t bytes) {
 
 int32_t bt_set_boot_row(bt_engine* e, int32_t mode) {
     ABI_GUARD(-1, { return set_knob(e, "bt_set_boot_row", "mode", mode, 2, &EngineState::boot_row); })
+}
+
+int32_t bt_drawdown_boot(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar, int32_t B,
+                         int32_t L, uint64_t seed, int32_t Q, const int32_t* alpha_ppm, int32_t R, const int64_t* limits,
+                         bt_dd_lane* lanes_out, int64_t* q_out, int64_t* reach_out, int64_t* raw_out) {
+    ABI_GUARD(-1, {
+        return drawdown_boot_impl(e, n, lanes, from_bar, to_bar, B, L, seed, Q, alpha_ppm, R, limits,
+                                  DdOut{lanes_out, q_out, reach_out, raw_out});
+    })
+}
+
+int32_t bt_drawdown_boot_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t B, int32_t L, uint64_t seed,
+                            int32_t Q, const int32_t* alpha_ppm, int32_t R, const int64_t* limits, bt_dd_lane* lanes_out,
+                            int64_t* q_out, int64_t* reach_out, int64_t* raw_out) {
+    ABI_GUARD(-1, {
+        return drawdown_boot_of_impl(e, n, T, d, B, L, seed, Q, alpha_ppm, R, limits,
+                                     DdOut{lanes_out, q_out, reach_out, raw_out});
+    })
+}
+
+int32_t bt_set_ddboot_budget(bt_engine* e, int64_t bytes) {
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_ddboot_budget", "bytes", bytes, -1, &EngineState::ddboot_budget); })
+}
+
+int32_t bt_set_ddboot_row(bt_engine* e, int32_t mode) {
+    ABI_GUARD(-1, { return set_knob(e, "bt_set_ddboot_row", "mode", mode, 2, &EngineState::ddboot_row); })
+}
+
+int32_t bt_last_ddboot_row(bt_engine* e) {
+    ABI_GUARD(-1, { return last_ddboot_row_impl(e); })
 }
 
 int32_t bt_set_surface_chunks(bt_engine* e, int32_t chunks) {

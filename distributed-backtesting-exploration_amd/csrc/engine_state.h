@@ -119,6 +119,9 @@ struct EngineState {
     int32_t last_tail_row = 0;     // bt_last_tail_row: the home the last bt_tail / bt_tail_of used
     int64_t boot_budget = 0;       // bt_set_boot_budget (0 = kBootBudget)
     int32_t boot_row = 0;          // bt_set_boot_row (0 = the planner's choice, 1 = LDS, 2 = arena)
+    int64_t ddboot_budget = 0;     // bt_set_ddboot_budget (0 = kDdBudget)
+    int32_t ddboot_row = 0;        // bt_set_ddboot_row (0 = the planner's choice, 1 = LDS, 2 = arena)
+    int32_t last_ddboot_row = 0;   // bt_last_ddboot_row: the home the last drawdown bootstrap used
     int32_t portfolio_replicas = 0;  // bt_set_portfolio_replicas (0 = the planner's choice)
     PinnedBuf<uint8_t> h_portfolio;  // the rows and the summary of one portfolio
     int32_t gram_split = 0;          // bt_set_gram_split (0 = the planner's choice)

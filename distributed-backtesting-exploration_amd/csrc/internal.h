@@ -307,6 +307,37 @@ hipError_t launch_boot_walk(const BootArgs& a, int32_t m, const BootPlan& pl, co
 hipError_t launch_boot_prefix(const BootArgs& a, int32_t m, const BootPlan& pl, hipStream_t st);
 hipError_t launch_boot_finish(const BootArgs& a, const BootPlan& pl, hipStream_t st);
 
+// Drawdown bootstrap (k_ddboot.hip, bt_drawdown_boot / bt_drawdown_boot_of; docs/drawdown_spec.md)
+// of one chunk of m lanes, one workgroup each, over the start table launch_boot_starts made: with
+// `lanes` the chunk's staged requests, with `d` its staged rows of increments, else lane lane0 +
+// blockIdx.x of the dataset, row * P + param. Every output is the chunk's own and may be nullptr.
+struct DdArgs {
+    const SymDesc* syms;           // all-lanes mode: the dataset's rows
+    const LaneRef* lanes;          // [m] the chunk's requests (list mode), else nullptr
+    const int32_t* d;              // [m][d_pitch] staged increments, else nullptr
+    const int32_t* starts;         // [K][B]
+    const int32_t* levels;         // [Q] alpha_ppm
+    const int64_t* limits;         // [R]
+    unsigned char* rows;           // [m][pitch] bytes: the arena rows (prefix row, then the tables), else nullptr
+    int64_t* vals;                 // [m][v_pitch]: the values of the selection when they are neither in LDS nor in raw
+    int64_t* raw;                  // [m][B] or nullptr
+    bt_dd_lane* rec;               // [m] or nullptr
+    int64_t* q;                    // [m][Q] or nullptr
+    int64_t* reach;                // [m][R] or nullptr
+    int64_t lane0;                 // the chunk's first lane (all-lanes mode)
+    int64_t pitch, d_pitch, v_pitch;
+    uint32_t r_w1, r_w2;           // bytes from the row's start to the two tables (equal: one table)
+    uint32_t l_vals;               // bytes from the start of LDS to the values of the selection (0: not in LDS)
+    int32_t P;
+    int32_t from, T, B, Lp, K, last_len, Q, R;
+};
+struct DdPlan;
+// Once a call, before its chunks: asks for the dynamic LDS of the call's kernel where it passes 64 KB.
+hipError_t prepare_dd(const DdPlan& pl, bool staged, const Grid& g);
+hipError_t launch_dd_walk(const DdArgs& a, int32_t m, const DdPlan& pl, const int32_t* high, const int32_t* low,
+                          const int32_t* close, const Grid& g, hipStream_t st);
+hipError_t launch_dd_of(const DdArgs& a, int32_t m, const DdPlan& pl, hipStream_t st);
+
 // Portfolio of chosen lanes (k_portfolio.hip, bt_portfolio; docs/portfolio_spec.md). The walk (one
 // wave64 workgroup per entry) adds every entry's per-bar pnl and position into replicated per-bar
 // accumulators with integer atomics; the finish (one block) folds the replicas into the output

@@ -695,6 +695,66 @@ BootPlan plan_boot(int64_t n, int64_t G, int32_t T, int32_t B, int32_t L, bool l
     return pl;
 }
 
+// ------------------------------------------------------------------------ drawdown bootstrap
+DdPlan plan_ddboot(int64_t n, int32_t T, int32_t B, int32_t L, int32_t Q, int32_t R, bool list, bool staged,
+                   bool want_raw, int cus, int32_t row_req, int64_t budget_req) {
+    (void)cus;                                     // one workgroup per lane whatever the device
+    constexpr int64_t kMaxGrid = 1LL << 30;        // one grid index per lane of a chunk
+    DdPlan pl{};
+    n = std::max<int64_t>(n, 1);
+    T = std::max(T, 1), B = std::max(B, 1), L = std::max(L, 1);
+    Q = std::min(std::max(Q, 0), (int32_t)BT_DD_LEVELS_MAX);
+    R = std::min(std::max(R, 0), (int32_t)BT_DD_LIMITS_MAX);
+    pl.T = T;
+    pl.Lp = std::min(L, T);
+    pl.K = (T + pl.Lp - 1) / pl.Lp;
+    pl.last_len = T - (pl.K - 1) * pl.Lp;
+    pl.two_tables = pl.K > 1 && pl.last_len != pl.Lp;
+    pl.block = 64 * kDdWaves;
+    pl.scan1 = dd_wave_scan(T, pl.Lp, pl.block);
+    pl.scan2 = dd_wave_scan(T, pl.last_len, pl.block);
+    const size_t table = (size_t)T * kDdEntryBytes;
+    pl.r_w1 = ((size_t)T + 1) * 8;
+    pl.r_w2 = pl.r_w1 + (pl.two_tables ? table : 0);
+    pl.row_bytes = pl.r_w2 + table;
+    const bool fits = kDdFixedBytes + pl.row_bytes <= kDdLdsBytes;
+    pl.row_refused = row_req == 1 && !fits;
+    pl.row_mode = row_req == 2 || !fits ? 2 : 1;
+    pl.lds_bytes = kDdFixedBytes + (pl.row_mode == 1 ? pl.row_bytes : 0);
+    const size_t vals_bytes = (size_t)B * 8;
+    if (Q > 0 && !want_raw && pl.lds_bytes + vals_bytes <= kDdLdsBytes) pl.l_vals = pl.lds_bytes, pl.lds_bytes += vals_bytes;
+    pl.pitch = pl.row_mode == 2 ? (int64_t)((pl.row_bytes + 255) / 256 * 256) : 0;
+    pl.v_pitch = Q > 0 && !want_raw && pl.l_vals == 0 ? ((int64_t)B + 31) / 32 * 32 : 0;
+    pl.d_pitch = staged ? ((int64_t)T + 63) / 64 * 64 : 0;
+    pl.starts_block = 256;
+    pl.starts_blocks = ((int64_t)pl.K * B + pl.starts_block - 1) / pl.starts_block;
+    const size_t budget = budget_req > 0 ? (size_t)budget_req : kDdBudget;
+    Carve c;
+    pl.o_starts = c.take((size_t)pl.K * (size_t)B * 4);
+    pl.o_levels = c.take((size_t)Q * 4);
+    pl.o_limits = c.take((size_t)R * 8);
+    pl.unit_bytes = (list ? sizeof(LaneRef) : 0) + sizeof(bt_dd_lane) + (size_t)Q * 8 + (size_t)R * 8 +
+                    (want_raw ? vals_bytes : 0) + (size_t)pl.pitch + (size_t)pl.v_pitch * 8 + (size_t)pl.d_pitch * 4;
+    // the chunk's eight regions each round up by less than kStagingAlign
+    const size_t fixed = c.end + 8 * kStagingAlign;
+    pl.need_bytes = fixed + pl.unit_bytes;
+    int64_t per = budget > fixed ? (int64_t)((budget - fixed) / pl.unit_bytes) : 0;
+    per = std::min(std::min(per, kMaxGrid), n);
+    pl.per_chunk = (int32_t)per;
+    pl.chunks = per > 0 ? (int32_t)((n + per - 1) / per) : 0;
+    const size_t m = (size_t)per;
+    pl.o_lanes = c.take(list ? m * sizeof(LaneRef) : 0);
+    pl.o_rec = c.take(m * sizeof(bt_dd_lane));
+    pl.o_q = c.take(m * (size_t)Q * 8);
+    pl.o_reach = c.take(m * (size_t)R * 8);
+    pl.o_raw = c.take(want_raw ? m * vals_bytes : 0);
+    pl.o_rows = c.take(m * (size_t)pl.pitch);
+    pl.o_vals = c.take(m * (size_t)pl.v_pitch * 8);
+    pl.o_d = c.take(m * (size_t)pl.d_pitch * 4);
+    pl.staging_bytes = per > 0 ? c.staging_bytes() : 0;
+    return pl;
+}
+
 // ------------------------------------------------------------------------ portfolio of lanes
 PortfolioPlan plan_portfolio(int32_t n, int32_t T, int cus, int32_t replicas_req, size_t budget_req) {
     PortfolioPlan pl{};

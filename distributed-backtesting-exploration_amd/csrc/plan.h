@@ -301,6 +301,66 @@ struct BootPlan {
 BootPlan plan_boot(int64_t n, int64_t G, int32_t T, int32_t B, int32_t L, bool list, bool staged, bool want_boot,
                    int cus, int32_t row_req = 0, int64_t budget_req = 0);
 
+// What a drawdown bootstrap (k_ddboot.hip, bt_drawdown_boot / bt_drawdown_boot_of) of n lanes over
+// T bars, B resamples in blocks of L bars, Q levels and R limits, is launched with. The blocks are
+// plan_boot's: Lp, K, last_len; two_tables: last_len differs from Lp and K > 1, so that the last
+// block needs a table of its own. A lane's row is its prefix row of T + 1 words, then one or two
+// tables of T entries of kDdEntryBytes (r_w1, r_w2: bytes from the row's start; equal with one
+// table). It lives in dynamic LDS behind kDdFixedBytes of histograms and scratch (row_mode 1) while
+// it fits kDdLdsBytes, a CU's whole LDS (above 64 KB the launcher asks for it with
+// hipFuncSetAttribute, and the CU then holds one workgroup: measured 3.5 times faster than arena
+// rows on a config-2 row of 80 KB), else in the arena (row_mode 2) in rows of
+// `pitch` bytes, whole 256-byte lines. row_refused: bt_set_ddboot_row(e, 1) with a row that does
+// not fit.
+// With Q > 0 the lane's B values stay for the selection: in its row of raw when raw is wanted, else
+// in LDS behind the row while they fit the same limit (l_vals: bytes from the start of LDS, 0: not
+// there), else in an arena row of v_pitch words. One workgroup of `block` threads per lane. Held
+// for the whole call: the start table [K][B] int32, the levels and the limits. Per chunk of
+// per_chunk lanes (the last one shorter; chunk c holds lanes [c * per_chunk, min(n, (c + 1) *
+// per_chunk)), every lane exactly once): the LaneRefs (list mode), the records, the quantiles, the
+// reach counts, a requested raw, the arena rows, the value rows and a staged call's increments
+// [per_chunk][d_pitch] int32. The whole never exceeds the budget; need_bytes is the staging of a call
+// with one lane per chunk, and per_chunk == 0 says that even that does not fit (the call is refused
+// with need_bytes named).
+constexpr size_t kDdBudget = 256u << 20;
+constexpr size_t kDdLdsBytes = 160 * 1024;     // dynamic LDS of a workgroup at most: the CU's
+constexpr size_t kDdFixedBytes = kTailHistBytes + 1024;   // the histograms and the workgroup's scratch
+constexpr size_t kDdEntryBytes = 24;           // a table entry: (h, l, dd)
+constexpr int32_t kDdWaves = 4;
+constexpr int64_t kDdScanCost = 8;             // a 64-bar tile scanned with the operator, in serial steps
+// The table of `len`-bar blocks over T bars by nthr threads: a wave scans a chunk (true) or a thread
+// walks one. nc chunks hold a start; the longer critical path loses.
+BT_HD inline bool dd_wave_scan(int32_t T, int32_t len, int32_t nthr) {
+    const int64_t nc = ((int64_t)T + len - 1) / len, nw = nthr / 64;
+    const int64_t serial = (int64_t)len * ((nc + nthr - 1) / nthr);
+    const int64_t scan = ((nc + nw - 1) / nw) * (((int64_t)len + 63) / 64) * kDdScanCost;
+    return scan < serial;
+}
+struct DdPlan {
+    int32_t T, Lp, K, last_len;
+    bool two_tables;
+    bool scan1, scan2;             // dd_wave_scan of the two tables, as the kernel itself evaluates it: for the
+                                   // plan driver and the tests, nothing is launched by them
+    int32_t row_mode;              // 1 = LDS, 2 = arena
+    bool row_refused;
+    size_t r_w1, r_w2, row_bytes;
+    int32_t block;
+    size_t lds_bytes, l_vals;      // dynamic LDS of a workgroup
+    int64_t pitch, d_pitch, v_pitch;
+    int32_t per_chunk, chunks;
+    int32_t starts_block;          // threads of a start-table block
+    int64_t starts_blocks;
+    size_t o_starts, o_levels, o_limits, o_lanes, o_rec, o_q, o_reach, o_raw, o_rows, o_vals, o_d;
+    size_t unit_bytes;             // per lane of a chunk
+    size_t need_bytes;
+    size_t staging_bytes;          // of a full chunk (0 with per_chunk == 0)
+};
+// `list`: the call has a lane list; `staged`: bt_drawdown_boot_of; neither: all-lanes mode. `row_req`:
+// bt_set_ddboot_row; `budget_req`: bt_set_ddboot_budget (0 = kDdBudget). `cus` is taken as every
+// plan function takes it and not used: one workgroup per lane whatever the device.
+DdPlan plan_ddboot(int64_t n, int32_t T, int32_t B, int32_t L, int32_t Q, int32_t R, bool list, bool staged,
+                   bool want_raw, int cus, int32_t row_req = 0, int64_t budget_req = 0);
+
 // What a portfolio (k_portfolio.hip, bt_portfolio) of n entries over T bars is launched with. The
 // walk's workgroups (one wave per entry) add into R replicas of two per-bar accumulators of
 // `pitch` 8-byte words each (entry b uses replica b % R), so that the waves, which all start at

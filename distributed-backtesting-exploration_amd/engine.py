@@ -1314,6 +1314,47 @@ class Engine:
         either way."""
         _check(sym("bt_set_boot_row")(self._h, mode))
 
+    # ---- drawdown bootstrap (ddrisk.py, k_ddboot.hip)
+    def drawdown_risk(self, lanes=None, resamples: int = 1000, block: int = 10, seed: int = 0, window=None,
+                      levels=(0.5, 0.95), limits=(), raw: bool = False):
+        """How deep could each lane's drawdown be (docs/drawdown_spec.md)? The circular block
+        bootstrap of reality_check (the same window, resamples, block and seed draw the same bars)
+        of every lane's largest drawdown: per lane the observed drawdown, how many resampled paths
+        reach it, the extremes and the exact sums of MDD* and MDD*^2, per level the quantile of
+        MDD*, per limit how many paths draw down at least that far. `lanes`: what replay takes;
+        without lanes every (symbol, param) lane of the resident dataset. `levels`: at most 8,
+        fractions (0.95) or integer parts per million; `limits`: at most 8 losses in ticks; `raw`
+        asks for the raw MDD* (with lanes only). run() need not have been called. The binding and
+        the result type (DrawdownRisk) live in ddrisk.py."""
+        from .ddrisk import engine_drawdown_risk
+        return engine_drawdown_risk(self, lanes, resamples, block, seed, window, levels, limits, raw)
+
+    def drawdown_of(self, d, resamples: int = 1000, block: int = 10, seed: int = 0, levels=(0.5, 0.95), limits=(),
+                    raw: bool = False):
+        """The drawdown kernels on a caller's increments: an [n, T] integer array with |d| < 2^31,
+        n at most BOOT_MAX. Needs no dataset."""
+        from .ddrisk import engine_drawdown_of
+        return engine_drawdown_of(self, d, resamples, block, seed, levels, limits, raw)
+
+    def set_ddboot_row(self, mode: int) -> None:
+        """Where drawdown_risk and drawdown_of keep a lane's prefix row and block tables: 0 = the
+        planner's choice, 1 = LDS (refused at call time when they do not fit), 2 = device memory.
+        Results are identical either way."""
+        from .ddrisk import engine_set_ddboot_row
+        engine_set_ddboot_row(self, mode)
+
+    def set_ddboot_budget(self, nbytes: int) -> None:
+        """Device staging budget of drawdown_risk and drawdown_of in bytes: 0 = the default
+        (256 MB). Results are identical whatever the budget."""
+        from .ddrisk import engine_set_ddboot_budget
+        engine_set_ddboot_budget(self, nbytes)
+
+    def last_ddboot_row(self) -> int:
+        """The row home the last drawdown_risk / drawdown_of used: 1 = LDS, 2 = device memory, 0 =
+        none yet."""
+        from .ddrisk import engine_last_ddboot_row
+        return engine_last_ddboot_row(self)
+
     # ---- portfolio of chosen lanes (bt_portfolio, k_portfolio.hip)
     def portfolio(self, lanes, windows=None, n_bars=None) -> Portfolio:
         """Trade chosen (symbol id, param) lanes of the resident dataset together (bt_portfolio):

@@ -666,6 +666,68 @@ int32_t bt_bootstrap_host(int32_t n, const int64_t* equity, const int32_t* n_bar
                           const int32_t* goff, int32_t from_bar, int32_t to_bar, int32_t B, int32_t L,
                           uint64_t seed, bt_boot_group* groups_out, bt_boot_lane* lanes_out, int64_t* vmax_out,
                           int64_t* boot_out);
+/* ---- drawdown bootstrap (k_ddboot.hip, ddboot.cpp; semantics: docs/drawdown_spec.md).
+ * How deep could each lane's drawdown be? The circular block bootstrap of bt_bootstrap (the same
+ * window rule, T, L', K, truncated last block, draws and modulo: a call with the same window, B, L
+ * and seed draws the same bars) applied to a path functional: MDD(x) = max over m of (peak_m - X_m),
+ * X_m the sum of the first m values, peak_m = max(0, X_1 .. X_m). Per lane mdd = MDD of the
+ * window's increments (with the default window the run's summary mdd), and MDD*_(i,b) = MDD of the
+ * T bars resample b draws, 0 <= MDD* < 2^53.
+ *   lanes_out[i]     bt_dd_lane: sum = S_i, mdd, n_ge = #{b : MDD* >= mdd}, min_star and max_star
+ *                    over b, m1 = sum over b of MDD*, m2 = sum over b of MDD*^2;
+ *   q_out[i*Q + j]   the k_j-th smallest MDD* of lane i, k_j = ceil(B * alpha_ppm[j] / 10^6);
+ *   reach_out[i*R+r] #{b : MDD* >= limits[r]};
+ *   raw_out[i*B + b] the raw MDD* (list mode and bt_drawdown_boot_of only).
+ * Q in [0, BT_DD_LEVELS_MAX] levels in [1, 10^6] ppm, R in [0, BT_DD_LIMITS_MAX] limits >= 0 in
+ * ticks, in any order, repeats allowed. There are no groups: every figure depends on its lane
+ * alone, so shards called with one explicit window concatenate.
+ *   list mode (lanes != NULL): n in [1, BT_BOOT_MAX] lanes in request order, repeats allowed;
+ *   all-lanes mode (lanes == NULL, n == 0): every lane of the dataset, row-major [S][P]; raw_out
+ *     must be NULL.
+ * Any output may be NULL, not all (q_out counts with Q > 0, reach_out with R > 0). Synchronous like
+ * bt_replay; nothing another entry point reads changes. Added within ABI 3 (additive). Returns 0, or
+ * -1 with bt_last_error naming the offending value (the engine stays usable): bt_bootstrap's own
+ * refusals of the engine, the dataset, n, the lanes, from_bar, T, B and L, Q or R outside [0, 8], a
+ * level or a limit out of range (its index named), all outputs NULL, raw_out in all-lanes mode, a
+ * staging need above the budget (the bytes named), a row that does not fit LDS under
+ * bt_set_ddboot_row(e, 1). */
+typedef struct bt_dd_lane {           /* 72 bytes */
+    int64_t sum;                                    /* S_i */
+    int64_t mdd;                                    /* the observed largest drawdown */
+    int64_t n_ge;                                   /* resamples with MDD* >= mdd */
+    int64_t min_star, max_star;                     /* smallest and largest MDD* */
+    bt_wide m1, m2;                                 /* sum of MDD*, sum of MDD*^2 over the B resamples */
+} bt_dd_lane;
+#define BT_DD_LEVELS_MAX 8
+#define BT_DD_LIMITS_MAX 8
+int32_t bt_drawdown_boot(bt_engine* e, int32_t n, const bt_lane* lanes, int32_t from_bar, int32_t to_bar, int32_t B,
+                         int32_t L, uint64_t seed, int32_t Q, const int32_t* alpha_ppm, int32_t R,
+                         const int64_t* limits,
+                         bt_dd_lane* lanes_out,       /* [n] or NULL */
+                         int64_t* q_out,              /* [n * Q] or NULL */
+                         int64_t* reach_out,          /* [n * R] or NULL */
+                         int64_t* raw_out);           /* [n * B] or NULL */
+/* The same on a caller's increments d[n][T] (row-major int32, INT32_MIN refused with its index),
+ * on any engine (also one without a dataset). n in [1, BT_BOOT_MAX], T in [1, 2^22]. */
+int32_t bt_drawdown_boot_of(bt_engine* e, int32_t n, int32_t T, const int32_t* d, int32_t B, int32_t L, uint64_t seed,
+                            int32_t Q, const int32_t* alpha_ppm, int32_t R, const int64_t* limits,
+                            bt_dd_lane* lanes_out, int64_t* q_out, int64_t* reach_out, int64_t* raw_out);
+/* bt_set_ddboot_budget: the device staging budget in bytes, 0 = the default (256 MB).
+ * bt_set_ddboot_row: where a lane's prefix row and block tables live: 0 = the planner's choice, 1 =
+ * LDS (a call whose row does not fit is refused), 2 = device memory. Results are identical under
+ * every setting. bt_last_ddboot_row: the home the last call of this engine used (1 or 2; 0 before
+ * the first). */
+int32_t bt_set_ddboot_budget(bt_engine* e, int64_t bytes);
+int32_t bt_set_ddboot_row(bt_engine* e, int32_t mode);
+int32_t bt_last_ddboot_row(bt_engine* e);
+/* Host, no GPU needed: the scalar restatement from replayed curves (equity rows of `stride` values,
+ * n_bars[i] bars each), which adds the drawn bars one by one and walks every resampled path: no
+ * prefix row, no block table. from_bar = to_bar = 0 means [0, max n_bars). It sorts every lane's B
+ * values. */
+int32_t bt_drawdown_boot_host(int32_t n, const int64_t* equity, const int32_t* n_bars, int64_t stride, int32_t from_bar,
+                              int32_t to_bar, int32_t B, int32_t L, uint64_t seed, int32_t Q, const int32_t* alpha_ppm,
+                              int32_t R, const int64_t* limits, bt_dd_lane* lanes_out, int64_t* q_out,
+                              int64_t* reach_out, int64_t* raw_out);
 /* ---- probability of backtest overfitting (k_cscv.hip, cscv.cpp; semantics: docs/cscv_spec.md).
  * How often does "pick the best lane in-sample" choose a lane that is below the median out of
  * sample? Combinatorially symmetric cross-validation over the fold records of bt_walk_forward: the
